@@ -2,7 +2,14 @@
 """
 Benchmark of the hologram optimize() hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg2|...] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg2|...] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (W steps), times ONE region of exactly K steps, writes the outputs of the last step if
+``--dump-outputs DIR`` is given, and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+Everything else described below -- the forty-region median, ``event_ms_per_step``, the roofline pass and its PMC child
+passes, the engine-default pass, the CPU baseline, refbench's four methods, and with several ranks the solo pass, the
+one-hologram-per-GPU rate and the final gather -- runs with ``--full`` only; the line carries those fields as null or
+leaves them out otherwise.
 
 ``--gpus N`` with N > 1 needs N ranks, one per GPU.  Under a launcher (the driver's ``python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N``) the ranks come from RANK / LOCAL_RANK / WORLD_SIZE; called plainly,
@@ -39,9 +46,9 @@ Workloads (``--workload``):
              them (host bookkeeping and the trailing transform included); --steps = maxiter; the four methods of the
              reference's parametrisation are all timed (``methods``), ``value`` is --method (default WGS-Leonardo)
 
-Timing protocol: W warm-up steps, then ``--reps`` (default 40) repetitions of the timed region -- EXACTLY K
-steps between barrier + synchronize on both sides, the slowest rank counting -- and ``value`` is K / the MEDIAN
-repetition; the spread is reported (``ms_per_step_min`` / ``_max``; the first regions after a short warm-up run on clocks
+Timing protocol: W warm-up steps, then ``--reps`` (default 1; 40 with --full) repetitions of the timed
+region -- EXACTLY K steps between barrier + synchronize on both sides, the slowest rank counting -- and ``value`` is K / the
+MEDIAN repetition; the spread is reported (``ms_per_step_min`` / ``_max``; the first regions after a short warm-up run on clocks
 that are still settling, which is why there are forty of them), with more than one rank also the rate of every
 rank (``per_rank_its``) so that a straggler shows.
 The region holds the K steps and nothing else (``hgs_iterate``); ``event_ms_per_step`` -- HIP events around the same K steps,
@@ -106,10 +113,19 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="K steps per timed repetition (default 200; refbench: 20)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=40,
-                    help="repetitions of the K-step timed region; the median is reported (min / max beside it).  40 because the "
-                         "GPU's clocks take about 15 ms of work to settle after an idle spell: with ten 20-step regions (16 ms) the "
-                         "median still sat on the ramp (12.6 k it/s against 13.1 k after 200 warm-up steps, same regions)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the K-step timed region; the median is reported (min / max beside it).  Default 1 (the "
+                         "plain run times exactly K steps), 40 with --full: the GPU's clocks take about 15 ms of work to settle "
+                         "after an idle spell, and with ten 20-step regions (16 ms) the median still sat on the ramp (12.6 k it/s "
+                         "against 13.1 k after 200 warm-up steps, same regions)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: forty timed regions (median), the HIP-event figure, the roofline pass "
+                         "with its PMC child passes, the engine-default (sparse-column) pass, the CPU baseline, the reference's "
+                         "four methods (refbench) and, with several ranks, the solo pass, the one-hologram-per-GPU rate and the "
+                         "final all-gather of the phase masks.  Off: set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (phase masks, weights; rank 0) as "
+                         "DIR/<name>.npy in the workload's float dtype, at most 64 MB in all (a fixed, seeded sample of larger arrays)")
     ap.add_argument("--batch", type=int, default=None, help="independent holograms per GPU (cfg3: 8)")
     ap.add_argument("--streams", type=int, default=None,
                     help="stream groups a rank's holograms are split over (one engine and HIP stream each; launches of "
@@ -154,7 +170,13 @@ def parse():
         a.workload = "cfg2" if a.gpus == 1 else "cfg3"
     if a.steps is None:
         a.steps = 20 if a.workload == "refbench" else 200
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if a.reps is None:
+        a.reps = 40 if a.full else 1
     a.reps = max(1, a.reps)
+    if not a.full:                   # the plain run: the headline and nothing else
+        a.no_roofline_pass, a.no_extra_pass, a.cpu_iters, a.pmc = True, True, 0, 0
     if a.spots is None:
         a.spots = 1000 if a.workload == "cfg4zern" else 10000
     if a.batch is None:
@@ -197,6 +219,9 @@ class StubProblem:
 
     def phases_device(self, torch, device):
         return torch.full((self.args.batch,) + self.slm, float(self.rank), dtype=torch.float32)
+
+    def outputs(self):
+        return {"phase": np.full((self.args.batch,) + self.slm, float(self.rank), dtype=np.float32)}
 
     def close(self):
         pass
@@ -253,6 +278,7 @@ class GridProblem:
                 self.desc = "Hologram, dense random image target"
             kw = {}
             self.sparse_target = False
+        self.spot_index = kw.get("spot_index")
         phases = np.stack([synth.seed_phase(1000 * rank + 2 + i, self.slm, dtype=self.np_dtype) for i in range(args.batch)])
         self.hb = HologramBatch(self.shape, self.slm, target, phases, dtype=self.np_dtype, device=local_rank,
                                 streams=args.streams, **kw)
@@ -284,6 +310,15 @@ class GridProblem:
                         device=torch.device("cuda", device))
         self.hb.phases_into_device(t.data_ptr(), t.numel() * t.element_size())
         return t
+
+    def outputs(self):
+        """What HologramBatch hands its caller (the [batch, Sh, Sw] phase masks) and the WGS weights the next step starts
+        from: at the spot pixels for spot targets ([batch, spots], spot order), else the whole [batch, Ph, Pw] grid."""
+        from slmsuite_amd import _lib as L
+        w = self.hb.engine.get(L.WEIGHTS)
+        if self.spot_index is not None:
+            w = w[:, self.spot_index[1], self.spot_index[0]]
+        return {"phase": self.hb.phases(), "weights": w}
 
     def close(self):
         self.hb.close()
@@ -336,6 +371,10 @@ class CompressedProblem:
     def run_plain(self, n):
         self.run(n, events=False)
 
+    def outputs(self):
+        """The SLM phase and the per-spot weights, as the hologram's caller reads them."""
+        return {"phase": np.asarray(self.h.phase), "weights": np.asarray(self.h.weights)}
+
     def close(self):
         self.h._release_engine()
 
@@ -381,6 +420,11 @@ class RefBenchProblem:
         ts = sorted(self.run(n) for _ in range(reps))
         self.method = keep
         return ts[len(ts) // 2]
+
+    def outputs(self):
+        """What a caller of optimize() reads afterwards: phase, farfield amplitude (the trailing transform of the timed call)
+        and weights."""
+        return {"phase": np.asarray(self.h.phase), "amp_ff": np.asarray(self.h.amp_ff), "weights": np.asarray(self.h.weights)}
 
     def close(self):
         self.h._release_engine()
@@ -508,6 +552,30 @@ def cpu_baseline(args):
 
 
 # ---------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, for comparing two builds output for output
+# ---------------------------------------------------------------------------------------------------
+DUMP_BYTES = 63 * 10 ** 6                    # all arrays together (the files, headers included, stay under 64 MB)
+DUMP_SHARE = {"phase": 0.5, "weights": 0.25, "amp_ff": 0.25}
+
+
+def dump_outputs(outputs, out_dir):
+    """
+    ``outputs`` (name -> array) as ``out_dir/<name>.npy``, float32 or float64 as computed.  An array larger than its share of
+    DUMP_BYTES is replaced by a fixed sample: the flattened array at sorted indices drawn from a generator seeded with 0 (the
+    same positions in every run of the same arguments), stored flat.
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        cap = int(DUMP_BYTES * DUMP_SHARE.get(name, 0.1)) // a.itemsize
+        if a.size > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, cap))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+# ---------------------------------------------------------------------------------------------------
 # PMC traffic, measured in this run: child passes of this script under rocprofv3
 # ---------------------------------------------------------------------------------------------------
 def main():
@@ -577,21 +645,22 @@ def main():
         return
     # timed region, --reps times: EXACTLY K steps between barrier + synchronize, the slowest rank counts
     # (alone: this rank by itself -- no barrier, nobody else's time -- while the others wait, see single_rank_same_job)
+    def sync_all(pb, alone=False):
+        pb.engine.sync()
+        cuda_sync()
+        if dist is not None and not alone:
+            dist.barrier(group=ctl)
+
     def timed_region(pb, alone=False):
-        def sync_all():
-            pb.engine.sync()
-            cuda_sync()
-            if dist is not None and not alone:
-                dist.barrier(group=ctl)
         ws, evs, rws = [], [], []
         # the wall-clock repetitions run the K steps and nothing else; the HIP-event figure of the same K steps (the roofline's
-        # time base) comes from a few repetitions of its own behind them
+        # time base) comes from a few repetitions of its own behind them (event_region, --full)
         plain = getattr(pb, "run_plain", None)
         for _ in range(args.reps):
-            sync_all()
+            sync_all(pb, alone)
             t0 = time.perf_counter()
             ms_ev = pb.run(args.steps) if plain is None else plain(args.steps)
-            sync_all()
+            sync_all(pb, alone)
             mine = time.perf_counter() - t0
             if dist is not None and not alone:        # the slowest rank counts
                 tmax = torch.tensor([mine], dtype=torch.float64, device=coll_dev)
@@ -601,16 +670,18 @@ def main():
                 dist.all_reduce(tmax, op=dist.ReduceOp.MAX, group=ctl)
                 mine = float(tmax.item())
             ws.append(mine)
-            evs.append(ms_ev)
-        if plain is not None:
-            ev = []
-            for _ in range(max(3, min(10, args.reps // 4))):
-                sync_all()
-                ev.append(pb.run(args.steps))
-            sync_all()
-            evs = [sorted(ev)[len(ev) // 2]] * len(ws)
+            evs.append(ms_ev if plain is None else None)
         mid_ = sorted(range(args.reps), key=lambda i: ws[i])[len(ws) // 2]
         return ws, evs, rws, mid_
+
+    def event_region(pb, alone=False):
+        """HIP-event milliseconds of K steps (median of a few repetitions), for problems whose timed regions run without them."""
+        ev = []
+        for _ in range(max(3, min(10, args.reps // 4))):
+            sync_all(pb, alone)
+            ev.append(pb.run(args.steps))
+        sync_all(pb, alone)
+        return sorted(ev)[len(ev) // 2]
 
     # Several ranks: first rank 0 ALONE on its own shard -- the very job it runs in the all-rank regions, the other ranks idle
     # at a barrier -- so that this one line carries its own scaling figure: `scaling_efficiency` = value / (N x that rate).
@@ -619,6 +690,8 @@ def main():
     if world > 1 and dist is not None and not args.no_extra_pass:
         if rank == 0:
             ws_, _, _, m_ = timed_region(prob, alone=True)
+            if hasattr(prob, "run_plain"):
+                event_region(prob, alone=True)
             solo = {"value": args.batch * args.steps / ws_[m_], "unit": "iterations/s", "ms_per_step": ws_[m_] * 1e3 / args.steps,
                     "what": "rank 0 alone on its shard of the job (same holograms, steps and repetitions; the other ranks wait at a "
                             "barrier), timed before the all-rank regions"}
@@ -626,6 +699,11 @@ def main():
 
     walls, events, rank_walls, mid = timed_region(prob)
     wall, ms_events = walls[mid], events[mid]
+    # the state now holds what the last timed step computed: dump it before anything else runs on it
+    if args.dump_outputs and rank == 0:
+        dump_outputs(prob.outputs(), args.dump_outputs)
+    if args.full and hasattr(prob, "run_plain"):
+        ms_events = event_region(prob)
 
     # several ranks on the default workload (cfg 3: eight holograms per GPU): the one-hologram-per-GPU rate as well, i.e.
     # the N = 1 default workload (cfg 2) on every rank, so that a scaling figure on EQUAL per-GPU work can be formed
@@ -835,10 +913,12 @@ def main():
                        "parallelism": f"independent holograms x{world}"},
             "repetitions": args.reps, "ms_per_step_min": min(walls) * 1e3 / args.steps,
             "ms_per_step_max": max(walls) * 1e3 / args.steps,
-            "timing": f"median of {args.reps} repetitions of the {args.steps}-step region (barrier + synchronize on both sides, "
-                      "max over ranks); state resident in HBM; the region holds the K steps only -- `event_ms_per_step` (HIP events "
-                      "around the same K steps) is taken in repetitions of its own, since round 6",
-            "event_ms_per_step": ms_events / args.steps, "gather_ms": gather_ms,
+            "timing": (f"median of {args.reps} repetitions of the {args.steps}-step region" if args.reps > 1 else
+                       f"one {args.steps}-step region after {args.warmup} warm-up steps") +
+                      " (barrier + synchronize on both sides, max over ranks); state resident in HBM; the region holds the K "
+                      "steps only -- `event_ms_per_step` (HIP events around the same K steps) is taken in repetitions of its own "
+                      "(--full)",
+            "event_ms_per_step": None if ms_events is None else ms_events / args.steps, "gather_ms": gather_ms,
             "engine": prob.engine.version(),
             "roofline": roof, "cpu_baseline": cpu,
         }
@@ -877,8 +957,8 @@ def main():
 
     # Final gather of the phase masks over RCCL, device memory -> RCCL, timed separately.  It runs AFTER the
     # line has been built from the timed regions and under a watchdog: a communicator that cannot be created or a collective
-    # that never returns costs the line its gather fields, not the measurement.
-    if dist is not None:
+    # that never returns costs the line its gather fields, not the measurement.  (--full: the plain run has no use for it.)
+    if dist is not None and args.full:
         import threading
         finished = threading.Event()
 

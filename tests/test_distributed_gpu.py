@@ -86,7 +86,7 @@ def test_bench_launches_its_own_ranks():
     the phase masks and its check on every rank -- is the path an 8-GPU node takes.
     """
     r, lines = _bench(["--gpus", "2", "--backend", "gloo", "--share-devices", "--steps", "4", "--warmup", "2", "--reps", "2",
-                       "--no-roofline-pass"])
+                       "--no-roofline-pass", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, r.stdout
     d = lines[0]
@@ -111,7 +111,7 @@ def test_bench_launches_its_own_ranks():
 def test_bench_one_rank_rccl_group():
     """The RCCL branch itself on the one device there is: a one-rank nccl group, gather included."""
     r, lines = _bench(["--gpus", "1", "--force-dist", "--workload", "small", "--batch", "3", "--steps", "4", "--warmup", "2",
-                       "--reps", "2", "--no-roofline-pass", "--cpu-iters", "0"])
+                       "--reps", "2", "--no-roofline-pass", "--full", "--cpu-iters", "0"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = lines[0]
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["process_group"]["backend"] == "nccl"
@@ -131,7 +131,7 @@ def test_bench_line_survives_a_gather_that_does_not_return():
     are still creating the group when the timer fires) the line comes out anyway -- value from the timed regions, the gather
     fields replaced by the reason -- and the launch ends with exit code 0."""
     r, lines = _bench(["--gpus", "2", "--backend", "gloo", "--share-devices", "--steps", "4", "--warmup", "2", "--reps", "2",
-                       "--no-roofline-pass", "--no-extra-pass", "--gather-timeout", "0"])
+                       "--no-roofline-pass", "--full", "--no-extra-pass", "--gather-timeout", "0"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, r.stdout
     d = lines[0]

@@ -501,7 +501,7 @@ def test_bench_n_ranks_line_is_self_contained():
     """
     import json
     r = _run_bench(["--gpus", "2", "--backend", "gloo", "--share-devices", "--no-roofline-pass", "--stub-engine",
-                    "--steps", "10", "--warmup", "1", "--reps", "5"])
+                    "--steps", "10", "--warmup", "1", "--reps", "5", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -527,6 +527,51 @@ def test_bench_stub_engine_is_only_the_rank_self_test():
     r = _run_bench(["--stub-engine", "--steps", "2", "--warmup", "1"])
     assert r.returncode != 0 and "self-test" in r.stderr
     assert not any(line.startswith("{") for line in r.stdout.splitlines())
+
+
+def test_bench_plain_line_times_exactly_k_steps_and_dumps(tmp_path):
+    """
+    A plain run (no --full) times one region of exactly --steps steps and prints the headline fields, with nothing of the
+    --full extras run: no roofline, no CPU baseline, no HIP-event repetitions.  --dump-outputs writes what the last step left
+    (the stand-in's phase masks) as float .npy files.  Stand-in engine: a step is a sleep of 0.2 ms per hologram.
+    """
+    import json
+    out = tmp_path / "dump"
+    r = _run_bench(["--backend", "gloo", "--share-devices", "--no-roofline-pass", "--stub-engine",
+                    "--steps", "25", "--warmup", "1", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 25 and d["repetitions"] == 1 and d["unit"] == "iterations/s" and d["higher_is_better"] is True
+    assert 0.2 <= d["ms_per_step"] < 20, d["ms_per_step"]                  # 25 sleeps of 0.2 ms in the region, nothing else
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "engine_default_path" not in d
+    ph = np.load(out / "phase.npy")
+    assert ph.dtype == np.float32 and ph.shape == (1, 16, 24) and np.all(ph == 0.0)
+
+
+def test_bench_dump_outputs_caps_the_size_with_a_fixed_sample(tmp_path):
+    """Arrays beyond their share of the 64 MB are replaced by the same seeded sample in every run; dtypes stay float32 /
+    float64; small arrays are written whole."""
+    sys.path.insert(0, ROOT)
+    import bench
+    big = np.arange(12_000_000, dtype=np.float64)                  # 96 MB
+    small = np.linspace(0, 1, 1000).astype(np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs({"weights": big, "phase": small, "amp_ff": big.astype(np.float32)}, str(tmp_path / d))
+    total = 0
+    for name in ("weights", "phase", "amp_ff"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        np.testing.assert_array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+    assert total <= 64 * 10 ** 6
+    w = np.load(tmp_path / "a" / "weights.npy")
+    assert w.dtype == np.float64 and 0 < w.size < big.size and np.all(np.diff(w) > 0)   # sorted, distinct positions
+    assert np.load(tmp_path / "a" / "amp_ff.npy").dtype == np.float32
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "phase.npy"), small)
 
 
 def test_update_flags_precedence_and_verbose_print(capsys):

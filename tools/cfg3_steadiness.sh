@@ -7,7 +7,7 @@ OUT=gpurun_out/cfg3_steadiness
 for i in $(seq 1 ${1:-10}); do
   clk=$(rocm-smi --showclocks 2>/dev/null | grep -E "sclk|mclk|fclk" | head -3 | sed 's/.*: *//' | tr '\n' ' ')
   tmp=$(rocm-smi --showtemp --showpower 2>/dev/null | grep -E "junction|Socket Power|Average Graphics" | head -2 | sed 's/.*: *//' | tr '\n' ' ')
-  timeout 300 python bench.py --workload cfg3 --steps 100 --warmup 10 --cpu-iters 0 --pmc 0 --no-extra-pass ${CFG3_ARGS} 2>/dev/null | grep '^{' | tee -a $OUT.jsonl | python -c "
+  timeout 300 python bench.py --full --workload cfg3 --steps 100 --warmup 10 --cpu-iters 0 --pmc 0 --no-extra-pass ${CFG3_ARGS} 2>/dev/null | grep '^{' | tee -a $OUT.jsonl | python -c "
 import sys,json
 for l in sys.stdin:
     d=json.loads(l); r=d['roofline']; print('run $i  it/s %8.0f  min %8.0f max %8.0f  col_us %6.1f row_us %6.1f | clocks: $clk | $tmp'%(d['value'], d['steps']/d['ms_per_step_max']*1e3*d['config']['holograms_per_gpu'], d['steps']/d['ms_per_step_min']*1e3*d['config']['holograms_per_gpu'], r['launch_us'], r['row_launch_us']))" | tee -a $OUT.txt

@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 for v in "$@"; do
   lib=slmsuite_amd/libhgs_$v.so; [ "$v" = main ] && lib=slmsuite_amd/libhgs.so
   for wl in ${WORKLOADS:-cfg2}; do
-  HGS_LIB=$PWD/$lib timeout 300 python bench.py --steps 200 --warmup 20 --cpu-iters 0 --pmc 0 --workload $wl $BENCH_ARGS 2>/dev/null | python -c "
+  HGS_LIB=$PWD/$lib timeout 300 python bench.py --full --steps 200 --warmup 20 --cpu-iters 0 --pmc 0 --workload $wl $BENCH_ARGS 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

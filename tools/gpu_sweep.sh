@@ -1,6 +1,6 @@
 #!/bin/bash
 # grid-size sweeps of the two hot kernels (developer overrides read once at hgs_create)
-run() { env "$@" timeout 300 python bench.py --steps 200 --warmup 20 --cpu-iters 0 --pmc 0 2>/dev/null | python -c "
+run() { env "$@" timeout 300 python bench.py --full --steps 200 --warmup 20 --cpu-iters 0 --pmc 0 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
