@@ -14,6 +14,7 @@
 
 #include "../../include/hgs.h"
 #include "launch.hpp"
+#include "column_plan.hpp"
 #include "compressed_kernels.hpp"
 #include "cgemm.hpp"
 #include "compressed_sep.hpp"
@@ -203,7 +204,6 @@ template <typename R> struct Engine : EngineBase {
     int* n_active_dev = nullptr;           // [B]
     unsigned short* lane_mask = nullptr;   // [B][Pw/16] row-kernel view of col_active
     unsigned short* lane_mask_noise = nullptr;   // ... of its bit 4: columns with a NaN target (noise part of single-pass MRAF)
-    int opt_gh2_mask = 1;                  // developer A/B (HGS_GH2_MASK=0 at create): noise part stored / read for every column
     // the same for the columns the spot integration windows touch (spot feedback / spot statistics)
     unsigned char* col_active_d = nullptr;
     int* col_list_d = nullptr;
@@ -214,15 +214,12 @@ template <typename R> struct Engine : EngineBase {
     int n_active_max = 0, n_active_min = 0;
     bool sparse_dirty = true;
     bool sparse_tiles = false;             // the active set is whole 4-column tiles (the tile-resident kernel walks the list)
-    int opt_tile_list = 1;                 // developer A/B (HGS_TILE_LIST=0 at create): column lists always go to the per-column kernel
-    // engine policy (hgs_set_option); the grid-size tuning knobs are read from the environment once, in init()
-    int opt_sparse = 1;                    // HGS_OPT_SPARSE_COLUMNS
+    // engine policy (hgs_set_option) and the developer switches, read from the environment once, in init() (read_tuning)
+    Tuning tun;
     int opt_stepwise = 0;                  // HGS_OPT_FORCE_STEPWISE
-    int opt_tile = 1;                      // HGS_OPT_TILE_KERNEL
     int opt_separable = 1;                 // HGS_OPT_SEPARABLE
     int opt_sep_min = 96;                  // smallest spot count the matrix-core form is used for (tools/sep_crossover.py)
     int opt_roctx = 0;                     // HGS_OPT_ROCTX: roctx ranges around the operators
-    int opt_tile_rule = 1;                 // developer A/B (HGS_TILE_RULE=0 at create): rule-specialised tile kernels off
     // G left behind (round 5): the last launch of a fused float32 hgs_iterate call is row_kernel MODE 3 -- it writes the phase AND
     // the row-transformed field of the next body, every column of it -- and the next call (or hgs_nearfield2farfield) skips its
     // own first row launch while nothing that G depends on (phase, amplitude, kernel) has changed.
@@ -232,22 +229,6 @@ template <typename R> struct Engine : EngineBase {
     R* phase_prev = nullptr;
     bool have_prev = false;
     int opt_prev_phase = 0;
-    int opt_tile2 = 1;                     // developer A/B (HGS_TILE2=0 at create): half-width tile kernel off
-    int opt_tile2_phase2 = 1;              // ... its phase-reading form at 4096 rows, one hologram (HGS_TILE2_PHASE2=0 at create: col_tile_kernel)
-    int opt_tile2_min_batch = 1;           // ... smallest batch that runs it at 4096 rows (HGS_TILE2_MIN_BATCH)
-    int env_tile2_blocks = 0;              // ... its workgroups per launch over the batch (HGS_TILE2_BLOCKS; 0 = 3 x / 2 x #CU)
-    int opt_mono_tab = 1;                  // developer A/B (HGS_MONO_TAB=0 at create): per-pixel compressed kernels evaluate every monomial per spot
-    int opt_keep_g = 1;                    // developer A/B (HGS_KEEP_G=0 at create)
-    int opt_mraf_presum = 1;               // developer A/B (HGS_MRAF_PRESUM=0 at create: the two-inverse split form on every update)
-    int env_presum_blocks = 0, opt_presum_rows = 1;    // developer A/B (HGS_PRESUM_BLOCKS, HGS_PRESUM_ROWS at create)
-    int opt_fused_shift = 1;               // developer A/B (HGS_FUSED_SHIFT=0 at create): float64 per-column kernel unshifted (16 slots)
-    int opt_tile_nr4 = 1;                  // developer A/B (HGS_TILE_NR4=0 at create): slot-count instances of the rule kernels off (NR = 6 only)
-    int opt_tile_shift16 = 1;              // developer A/B (HGS_TILE_SHIFT16=0 at create): the tile kernel shifts by whole register slots
-    int opt_row_shift = 1;                 // developer A/B (HGS_ROW_SHIFT=0 at create): shifted row kernel off
-    int opt_row_shift64 = 1;               // ... in float64 (HGS_ROW_SHIFT64=0 at create; round 5)
-    int opt_row_pref = 1;                  // developer A/B (HGS_ROW_PREF=0 at create): prefetching row kernel off
-    int opt_mraf_split = 1;                // developer A/B (HGS_MRAF_SPLIT=0 at create): MRAF weight updates in two column passes
-    bool row_split = false;                // the next row kernel joins gh and gh2 (single-pass MRAF)
     // per-column kernel (float64; float32 where the tile-resident kernel does not run) single-pass MRAF: noise part as farfield
     // values, the columns that hold it, their inverse pass
     C* ffb = nullptr;                      // [B][P], layout of ff; only NaN-target pixels are ever written, the rest stays zero
@@ -261,8 +242,6 @@ template <typename R> struct Engine : EngineBase {
     int n_signal_max = 0;
     bool signal_valid = false;
     bool ffb_zeroed = false;               // ... and so do the zeros of ffb (written since at NaN-target pixels only)
-    bool row_split_noise_only = false;     // ... and the row kernel must read gh2 in those columns only (nothing else was written)
-    int opt_mraf_split64 = 1;              // developer A/B (HGS_MRAF_SPLIT64=0 at create): float64 MRAF weight updates in two passes
     int row_blocks_pref = 0;               // its grid: two workgroups per CU, whole XCD line groups
     // statistics of the fused path (hgs_iterate_stats)
     double* stats_scratch = nullptr;  // hgs_stats group 0: per-block partials of the two passes
@@ -325,7 +304,7 @@ template <typename R> struct Engine : EngineBase {
     // (||w'||^2 = 1 + D); every other writer of the weights or of wscale goes through fill_wscale_one and clears it.
     bool w_unit = false;
     bool has_target = false, has_spots = false;
-    int row_blocks = 0, col_blocks = 0, ew_blocks = 0, n_cu = 256, row_xcd = 0, tile_blocks = 0, wpartial_n = 0, col_xmap = 0, list_xmap = 0;
+    int row_blocks = 0, col_blocks = 0, ew_blocks = 0, n_cu = 256, row_xcd = 0, tile_blocks = 0, col_xmap = 0;
     // profiling
     bool prof = false;
     struct Ev { int kind; hipEvent_t a, b; };
@@ -378,6 +357,41 @@ template <typename R> struct Engine : EngineBase {
         return 0;
     }
 
+    // the developer switches, in the order include/hgs.h lists them: the one place the environment is read
+    static Tuning read_tuning(int n_cu, int pad_h) {
+        Tuning t;
+        t.row_blocks = env_int("HGS_ROW_BLOCKS", n_cu * 64);
+        t.col_blocks = env_int("HGS_COL_BLOCKS", n_cu * 3);
+        // (8192 rows: one workgroup fits a CU, so 2 x #CU workgroups run as two rounds whose first tile each comes without
+        //  the LDS staging of the previous one; one round of #CU workgroups with twice the tiles: cfg5pad 213.2 -> 209.6 us)
+        t.tile_blocks = env_int("HGS_TILE_BLOCKS", pad_h >= 8192 ? n_cu : n_cu * 2);
+        t.tile2_blocks = env_int("HGS_TILE2_BLOCKS", 0);
+        t.row_pref_blocks = env_int("HGS_ROW_PREF_BLOCKS", 2 * n_cu);
+        t.row_xcd = env_int("HGS_ROW_XCD", 1);
+        t.col_xmap = env_int("HGS_COL_XMAP", 1);
+        t.row_shift = env_int("HGS_ROW_SHIFT", 1);
+        t.row_shift64 = env_int("HGS_ROW_SHIFT64", 1);
+        t.row_pref = env_int("HGS_ROW_PREF", 1);
+        t.row_pref_batch = env_int("HGS_ROW_PREF_BATCH", 0);
+        t.tile_rule = env_int("HGS_TILE_RULE", 1);
+        t.mraf_split = env_int("HGS_MRAF_SPLIT", 1);
+        t.mraf_split64 = env_int("HGS_MRAF_SPLIT64", 1);
+        t.gh2_mask = env_int("HGS_GH2_MASK", 1);
+        t.tile_list = env_int("HGS_TILE_LIST", 1);
+        t.tile_shift16 = env_int("HGS_TILE_SHIFT16", 1);
+        t.tile_nr4 = env_int("HGS_TILE_NR4", 1);
+        t.tile2 = env_int("HGS_TILE2", 1);
+        t.tile2_min_batch = env_int("HGS_TILE2_MIN_BATCH", 1);
+        t.tile2_phase2 = env_int("HGS_TILE2_PHASE2", 1);
+        t.keep_g = env_int("HGS_KEEP_G", 1);
+        t.fused_shift = env_int("HGS_FUSED_SHIFT", 1);
+        t.mono_tab = env_int("HGS_MONO_TAB", 1);
+        t.mraf_presum = env_int("HGS_MRAF_PRESUM", 1);
+        t.presum_rows = env_int("HGS_PRESUM_ROWS", 1);
+        t.presum_blocks = env_int("HGS_PRESUM_BLOCKS", 0);
+        return t;
+    }
+
     int init(const hgs_config& c) override {
         cfg = c;
         device = c.device;
@@ -389,6 +403,7 @@ template <typename R> struct Engine : EngineBase {
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, c.device));
         n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        tun = read_tuning(n_cu, c.pad_h);
         if (c.kind == 1) return init_compressed(c);
         if (c.kind != 0) return fail(HGS_ERR_ARG, "unknown engine kind %d", c.kind);
         const bool fast = is_pow2(c.pad_h) && is_pow2(c.pad_w) && c.pad_h >= 64 && c.pad_w >= 64 && c.pad_h <= 8192 &&
@@ -414,25 +429,6 @@ template <typename R> struct Engine : EngineBase {
         P = (size_t)g.Ph * g.Pw;
         // HGS_TRACE_INIT=1: where hgs_create spends its time (developer aid, stderr)
         const bool trace_init = env_int("HGS_TRACE_INIT", 0) != 0;
-        opt_tile_rule = env_int("HGS_TILE_RULE", 1);
-        opt_tile_nr4 = env_int("HGS_TILE_NR4", 1);
-        opt_fused_shift = env_int("HGS_FUSED_SHIFT", 1);
-        opt_keep_g = env_int("HGS_KEEP_G", 1);
-        opt_tile2 = env_int("HGS_TILE2", 1);
-        opt_tile2_min_batch = env_int("HGS_TILE2_MIN_BATCH", 1);
-        opt_tile2_phase2 = env_int("HGS_TILE2_PHASE2", 1);
-        env_tile2_blocks = env_int("HGS_TILE2_BLOCKS", 0);
-        opt_tile_shift16 = env_int("HGS_TILE_SHIFT16", 1);
-        opt_row_pref = env_int("HGS_ROW_PREF", 1);
-        opt_mraf_split = env_int("HGS_MRAF_SPLIT", 1);
-        opt_mraf_split64 = env_int("HGS_MRAF_SPLIT64", 1);
-        opt_mraf_presum = env_int("HGS_MRAF_PRESUM", 1);
-        opt_presum_rows = env_int("HGS_PRESUM_ROWS", 1);
-        env_presum_blocks = env_int("HGS_PRESUM_BLOCKS", 0);
-        opt_gh2_mask = env_int("HGS_GH2_MASK", 1);
-        opt_tile_list = env_int("HGS_TILE_LIST", 1);
-        opt_row_shift = env_int("HGS_ROW_SHIFT", 1);
-        opt_row_shift64 = env_int("HGS_ROW_SHIFT64", 1);
         auto t_prev = std::chrono::steady_clock::now();
         auto lap = [&](const char* what) {
             if (!trace_init) return;
@@ -449,24 +445,24 @@ template <typename R> struct Engine : EngineBase {
         const int row_units = (g.Sh + fpw - 1) / fpw;
         // one-row workgroups balance best (the hardware dispatcher hands a free slot the next row); a batch keeps them up
         // to 64 workgroups per CU (cfg 3, 8 x 1152 rows: 187.6 -> 171.4 us per row launch against 256 per hologram)
-        int cap = env_int("HGS_ROW_BLOCKS", n_cu * 64);
+        int cap = tun.row_blocks;
         cap = cap / B > 0 ? cap / B : 1;
         int per = (row_units + cap - 1) / cap;
         row_blocks = (row_units + per - 1) / per;
         // XCD-aware row mapping (row_kernel): the 4 / fpw workgroups of a 128-byte line group on one XCD together
         const int grp = fpw <= 4 ? 4 / fpw : 1;
-        row_xcd = (grp > 1 && row_blocks >= 8 * grp && env_int("HGS_ROW_XCD", 1)) ? 1 : 0;
+        row_xcd = (grp > 1 && row_blocks >= 8 * grp && tun.row_xcd) ? 1 : 0;
         if (row_xcd) row_blocks = (row_blocks + 8 * grp - 1) / (8 * grp) * (8 * grp);
         // prefetching row kernel (one hologram; a batch keeps the one-row workgroups): 2 workgroups per CU
         // (round 5: a batch walks too where every workgroup gets at least four rows -- 8 x 1152 rows over 2 x #CU workgroups
         //  are 18 rows each, no partial round at all; HGS_ROW_PREF_BATCH=0 keeps its one-row workgroups)
         row_blocks_pref = 0;
-        if (sizeof(R) == 4 && g.Pw == 4096 && fpw == 1 && row_xcd && (B == 1 || env_int("HGS_ROW_PREF_BATCH", 0))) {
-            const int want = env_int("HGS_ROW_PREF_BLOCKS", 2 * n_cu) / B;
+        if (sizeof(R) == 4 && g.Pw == 4096 && fpw == 1 && row_xcd && (B == 1 || tun.row_pref_batch)) {
+            const int want = tun.row_pref_blocks / B;
             row_blocks_pref = std::max(8 * grp, want / (8 * grp) * (8 * grp));
         }
         const int tiles = g.Pw / 4;
-        cap = env_int("HGS_COL_BLOCKS", n_cu * 3);
+        cap = tun.col_blocks;
         cap = cap / B > 0 ? cap / B : 1;
         per = (tiles + cap - 1) / cap;
         col_blocks = (tiles + per - 1) / per;
@@ -474,10 +470,9 @@ template <typename R> struct Engine : EngineBase {
         // is a multiple of 8 * passes lets the passes of a tile run on one XCD at a time (ColArgs::col_xmap); among those
         // the one that wastes the least of its last sweep, the larger on a tie
         col_xmap = 0;
-        list_xmap = env_int("HGS_COL_XMAP", 1);
         {
             const int Tc = g.Ph / 16, cpar = Tc >= 256 ? 1 : std::min(4, 256 / Tc), passes = 4 / cpar, q = 8 * passes;
-            if (passes > 1 && env_int("HGS_COL_XMAP", 1)) {
+            if (passes > 1 && tun.col_xmap) {
                 double best = 0;
                 int best_g = 0;
                 for (int G = q; G <= cap && G / passes <= tiles; G += q) {
@@ -488,9 +483,7 @@ template <typename R> struct Engine : EngineBase {
                 if (best_g > 0 && best >= 0.9) { col_blocks = best_g; col_xmap = 1; }
             }
         }
-        // (8192 rows: one workgroup fits a CU, so 2 x #CU workgroups run as two rounds whose first tile each comes without
-        //  the LDS staging of the previous one; one round of #CU workgroups with twice the tiles: cfg5pad 213.2 -> 209.6 us)
-        tile_blocks = std::max(1, std::min(tiles, env_int("HGS_TILE_BLOCKS", g.Ph >= 8192 ? n_cu : n_cu * 2) / B));
+        tile_blocks = std::max(1, std::min(tiles, tun.tile_blocks / B));
         ew_blocks = (int)std::min<size_t>((P + 255) / 256, (size_t)std::max(1, n_cu * 8 / B));
 
         if (dalloc(&phase, B * S)) return HGS_ERR_DEVICE;
@@ -692,7 +685,6 @@ template <typename R> struct Engine : EngineBase {
     int init_compressed(const hgs_config& c) {
         if (c.n_spots < 1 || c.n_monomials < 1 || c.slm_h < 1 || c.slm_w < 1 || c.batch < 1)
             return fail(HGS_ERR_ARG, "compressed engine needs n_spots, n_monomials, slm shape and batch >= 1");
-        opt_mono_tab = env_int("HGS_MONO_TAB", 1);
         g.Sh = c.slm_h; g.Sw = c.slm_w; g.r0 = g.c0 = 0;
         g.Ph = c.n_spots; g.Pw = 1;      // farfield-sized arrays are N-vectors; the transposes degenerate
         g.batch = B = c.batch;
@@ -1021,7 +1013,7 @@ template <typename R> struct Engine : EngineBase {
             if (use_run()) { if (int e = run_n2f(a)) return e; }
             else if (c_degree <= 1) { dispatch_note(dispatch_site<KCn2fPix, R, 1>(), bflag()); hipLaunchKernelGGL((c_n2f_partial<R, 1>), grid, dim3(C_WG), 0, stream, a); }
             else if (c_degree == 2) { dispatch_note(dispatch_site<KCn2fPix, R, 2>(), bflag()); hipLaunchKernelGGL((c_n2f_partial<R, 2>), grid, dim3(C_WG), 0, stream, a); }
-            else if (cfg.n_monomials <= C_MTAB && opt_mono_tab) { dispatch_note(dispatch_site<KCn2fPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_n2f_partial<R, 3>), grid, dim3(C_WG), 0, stream, a); }
+            else if (cfg.n_monomials <= C_MTAB && tun.mono_tab) { dispatch_note(dispatch_site<KCn2fPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_n2f_partial<R, 3>), grid, dim3(C_WG), 0, stream, a); }
             else { dispatch_note(dispatch_site<KCn2fPix, R, 0>(), bflag()); hipLaunchKernelGGL((c_n2f_partial<R, 0>), grid, dim3(C_WG), 0, stream, a); }
             HIPCHK(hipGetLastError());
             hipLaunchKernelGGL(c_n2f_reduce<R>, dim3(nred, B), dim3(C_RED_SPOTS * C_RED_SLICES), 0, stream, a, cnorm);
@@ -1050,7 +1042,7 @@ template <typename R> struct Engine : EngineBase {
             if (use_run()) return run_f2n(a);
             if (c_degree <= 1) { dispatch_note(dispatch_site<KCf2nPix, R, 1>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 1>), grid, dim3(C_WG), 0, stream, a); }
             else if (c_degree == 2) { dispatch_note(dispatch_site<KCf2nPix, R, 2>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 2>), grid, dim3(C_WG), 0, stream, a); }
-            else if (cfg.n_monomials <= C_MTAB && opt_mono_tab) { dispatch_note(dispatch_site<KCf2nPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 3>), grid, dim3(C_WG), 0, stream, a); }
+            else if (cfg.n_monomials <= C_MTAB && tun.mono_tab) { dispatch_note(dispatch_site<KCf2nPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 3>), grid, dim3(C_WG), 0, stream, a); }
             else { dispatch_note(dispatch_site<KCf2nPix, R, 0>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 0>), grid, dim3(C_WG), 0, stream, a); }
             HIPCHK(hipGetLastError());
             return 0;
@@ -1058,63 +1050,6 @@ template <typename R> struct Engine : EngineBase {
         farfield_valid = false;
         return r;
     }
-
-    // per-column fused launch: rule-specialised kernel where the pass is plain (fp32, no statistics, no extras)
-    int fused_launch(int phase_mode, dim3 grid, const ColArgs<R>& a) {
-        if constexpr (sizeof(R) == 4) {
-            const bool plain = !a.do_stats && !a.cp.mraf && !a.cp.nog_pass && !a.cp.weights_only && a.cp.nog == nullptr;
-            if (plain && opt_tile_rule) {
-                if (!a.cp.do_update) return launch_fused_rule2(g.Ph, phase_mode, grid, stream, a);
-                if (a.cp.method == HGS_WGS_LEONARDO || a.cp.method == HGS_WGS_KIM) return launch_fused_rule1(g.Ph, phase_mode, grid, stream, a);
-            }
-        }
-        return launch_fused<R>(g.Ph, phase_mode, grid, stream, a);
-    }
-    // half-width tile-resident kernel (col_tile2_kernel): the grid it runs on, or 0 where it does not apply -- fp32, a dense
-    // launch of a plain pass (Leonardo / Kim update or none; no statistics, MRAF, Nogrette sum or forward-only pass), and
-    //   4096 rows: a batch (>= 2 holograms), farfield phase neither stored nor read (PHASE 0: the phase-storing instances do
-    //              not fit 168 registers), SLM rows within six slots -- 3 x #CU workgroups over the batch, a multiple of 16
-    //              per hologram so that the two halves of a tile run on one XCD together;
-    //   2048 rows: SLM rows within ten slots -- 2 x #CU workgroups of two lane groups, one tile each at a time.
-    int tile2_grid(bool sp, bool tile_path, const ColArgs<R>& a, int phase_mode) const {
-        // (HGS_OPT_TILE_KERNEL = 0 forces the per-column kernel at every size: the tests' A/B reference)
-        if (sizeof(R) != 4 || !opt_tile2 || !opt_tile || sp || a.do_stats || !opt_tile_rule) return 0;
-        if (a.cp.mraf || a.cp.nog_pass || a.cp.weights_only || a.cp.nog != nullptr) return 0;
-        if (a.cp.do_update && a.cp.method != HGS_WGS_LEONARDO && a.cp.method != HGS_WGS_KIM) return 0;
-        const int nr = tile_slots();
-        // the developer override HGS_TILE2_BLOCKS never exceeds what wpartial / the statistics partials are sized for
-        // (B * max(col_blocks, tile_blocks, 3 * #CU) entries) nor the number of half tiles there are
-        const int want = env_tile2_blocks > 0 ? std::min(env_tile2_blocks, 3 * n_cu) : 0;
-        if (g.Ph == 4096) {
-            if (B < opt_tile2_min_batch || (phase_mode != 0 && !(phase_mode == 2 && opt_tile2_phase2 && B == 1)) || !tile_path || !tile2_has(4096, nr)) return 0;
-            const int per = (want > 0 ? want : 3 * n_cu) / B;
-            return std::min(std::max(16, per / 16 * 16), std::max(16, g.Pw / 2 / 16 * 16));
-        }
-        if (g.Ph == 2048) {
-            if (!tile2_has(2048, nr)) return 0;
-            return std::max(1, std::min(g.Pw / 4, (want > 0 ? want : 2 * n_cu) / B));
-        }
-        return 0;
-    }
-    static int tile2_launch(int N, int phase, int rule, int nr, dim3 grid, hipStream_t s, const ColArgs<float>& a, int shift, int xmap) {
-        return launch_tile2(N, phase, rule, nr, grid, s, a, shift, xmap);
-    }
-    static int tile2_launch(int, int, int, int, dim3, hipStream_t, const ColArgs<double>&, int, int) { return (int)hipErrorInvalidValue; }
-    // (the tile-resident kernel is fp32 only; this branch is never taken for double)
-    static int tile_rule(int N, int phase, int rule, int nr, dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {
-        return a.col_list != nullptr ? launch_tile_rule_listed(N, phase, rule, nr, grid, s, a, m0) : launch_tile_rule(N, phase, rule, nr, grid, s, a, m0);
-    }
-    static int tile_rule(int, int, int, int, dim3, hipStream_t, const ColArgs<double>&, int) { return (int)hipErrorInvalidValue; }
-    static int tile_split(int N, int phase, int nr, int rule_ok, dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {
-        return a.do_stats ? launch_tile_split_stats(N, phase, nr, rule_ok, grid, s, a, m0) : launch_tile_split(N, phase, nr, rule_ok, grid, s, a, m0);
-    }
-    static int tile_split(int, int, int, int, dim3, hipStream_t, const ColArgs<double>&, int) { return (int)hipErrorInvalidValue; }
-    static int presum_launch(int N, int nr, dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) { return launch_presum(N, nr, grid, s, a, m0); }
-    static int presum_launch(int, int, dim3, hipStream_t, const ColArgs<double>&, int) { return (int)hipErrorInvalidValue; }
-    static int tile_presum(int N, int phase, int nr, dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) { return launch_tile_presum(N, phase, nr, grid, s, a, m0); }
-    static int tile_presum(int, int, int, dim3, hipStream_t, const ColArgs<double>&, int) { return (int)hipErrorInvalidValue; }
-    static int row_split_launch(int N, int mode, dim3 grid, hipStream_t s, const RowArgs<float>& a) { return launch_row_split(N, mode, grid, s, a); }
-    static int row_split_launch(int N, int mode, dim3 grid, hipStream_t s, const RowArgs<double>& a) { return launch_row_split(N, mode, grid, s, a); }
 
     int fill_wscale_one() {
         hipLaunchKernelGGL(set_scalar<R>, dim3((B + 63) / 64), dim3(64), 0, stream, wscale, B, (R)1);
@@ -1497,31 +1432,32 @@ template <typename R> struct Engine : EngineBase {
     }
 
     // ---- operator launches ----
-    RowArgs<R> row_args(bool finalize) {
+    RowArgs<R> row_args(bool finalize, int n_wpartial = 0) {
         RowArgs<R> a{};
         a.g = g; a.phase = phase; a.amp = has_amp ? amp : nullptr; a.kern = has_kern ? kern : nullptr;
         a.amp_scalar = (R)amp_scalar; a.gh = gh; a.tw = tw_row; a.scale = (R)(1.0 / std::sqrt((double)g.Pw));
-        a.wpartial = finalize ? wpartial : nullptr; a.n_wpartial = wpartial_n; a.wscale = wscale;
+        a.wpartial = finalize ? wpartial : nullptr; a.n_wpartial = n_wpartial; a.wscale = wscale;
         a.xcd_map = row_xcd;
         a.n_row_blocks = row_blocks;
         {   // shifted form of the row kernel: fp32, one-row workgroups, the SLM columns within eight register slots
             const int T = g.Pw / 16;
             const int s0 = g.c0 / T, s1 = (g.c0 + g.Sw - 1) / T;
-            a.shifted = ((sizeof(R) == 4 || opt_row_shift64) && g.Pw >= 4096 && s1 - s0 + 1 <= 8 && opt_row_shift) ? 1 : 0;
+            a.shifted = ((sizeof(R) == 4 || tun.row_shift64) && g.Pw >= 4096 && s1 - s0 + 1 <= 8 && tun.row_shift) ? 1 : 0;
             a.m0 = s0;
         }
         return a;
     }
     // load / store: 0 = every column, 1 = active columns, 2 = active columns dilated by the spot windows
     // mode: row_kernel MODE (3 = MODE 2 that also writes the phase; float32 only)
-    int run_row(int mode, bool finalize, int load_sparse = 0, int store_sparse = 0) {
+    // cp: the column pass this launch closes (the partials it folds, the join of a single-pass MRAF body), or null
+    int run_row(int mode, bool finalize, int load_sparse = 0, int store_sparse = 0, const ColumnPlan* cp = nullptr) {
         gh_state = -1;
-        int r_ = run_row_impl(mode, finalize, load_sparse, store_sparse);
+        int r_ = run_row_impl(mode, finalize, load_sparse, store_sparse, cp);
         if (r_ == 0 && mode != 1) gh_state = store_sparse;      // gh holds G of the columns this launch stored
         return r_;
     }
     // (fused loops only; p = the plan of the call's first iteration)
-    template <typename PlanT> int keep_prev_phase(const PlanT& p, int n) {
+    int keep_prev_phase(const Plan& p, int n) {
         if (!opt_prev_phase) return 0;
         if (n != 1) { have_prev = false; return 0; }      // the phases in between are never materialised
         if (p.use_fixed) return 0;                          // phase_ff is not rewritten: what is held stays what describes it
@@ -1530,10 +1466,10 @@ template <typename R> struct Engine : EngineBase {
         have_prev = true;
         return 0;
     }
-    bool gh_holds(int need) const { return opt_keep_g && (gh_state == need || gh_state == 0 || (gh_state == 2 && need == 1 && dil_valid)); }
-    int run_row_impl(int mode, bool finalize, int load_sparse, int store_sparse) {
+    bool gh_holds(int need) const { return tun.keep_g && (gh_state == need || gh_state == 0 || (gh_state == 2 && need == 1 && dil_valid)); }
+    int run_row_impl(int mode, bool finalize, int load_sparse, int store_sparse, const ColumnPlan* cp) {
         return timed(HGS_K_ROW, [&]() -> int {
-            RowArgs<R> a = row_args(finalize);
+            RowArgs<R> a = row_args(finalize, cp ? cp->wpartial_n : 0);
             a.load_mask = load_sparse == 1 ? lane_mask : load_sparse == 2 ? lane_mask_d : nullptr;
             a.store_mask = store_sparse == 1 ? lane_mask : store_sparse == 2 ? lane_mask_d : nullptr;
             // one extra (row-less) block folds the weight-norm partials when asked to
@@ -1542,21 +1478,17 @@ template <typename R> struct Engine : EngineBase {
             // (measured, tools/row_tail_probe.py: it pays where a one-row-per-workgroup launch ends in a partial round that the
             //  walk turns into a third row for a quarter to a half of the workgroups -- 1152 rows 28.1 -> 26.3 us, 1280 rows
             //  29.1 -> 27.5 us, 1040 / 1088 / 1200 / 1248 rows 1.0 - 1.7 us ahead; level at 1024 rows, behind at 1312 and 1536)
-            if (sizeof(R) == 4 && g.Pw == 4096 && mode == 2 && opt_row_pref && row_blocks_pref > 0 && !a.load_mask && !a.store_mask &&
+            if (sizeof(R) == 4 && g.Pw == 4096 && mode == 2 && tun.row_pref && row_blocks_pref > 0 && !a.load_mask && !a.store_mask &&
                 (B == 1 ? (g.Sh > 2 * row_blocks_pref && 2 * g.Sh <= 5 * row_blocks_pref) : g.Sh >= 4 * row_blocks_pref)) {
                 a.prefetch = 1;
                 a.n_row_blocks = blocks = row_blocks_pref;
             }
-            if (row_split) {          // single-pass MRAF: H = gh * wscale + gh2 (wscale final: scale_from_sum ran)
+            if (cp && cp->join != RowJoin::none) {          // single-pass MRAF: H = gh * wscale + gh2 (wscale final: scale_from_sum ran)
                 a.prefetch = 0;
                 a.n_row_blocks = blocks = row_blocks;
                 a.gh2 = gh2;
-                // (a column-list launch already reads the listed columns only, and a noise box fills its list: there the
-                //  second mask costs its fetch -- 42.4 -> 46.1 us at cfg 5 -- and saves nothing)
-                a.gh2_mask = (row_split_noise_only || (opt_gh2_mask && !sparse_dirty && !a.load_mask)) ? lane_mask_noise : nullptr;
-                row_split = false;
-                row_split_noise_only = false;
-                LCHK(row_split_launch(g.Pw, mode, dim3(blocks, B), stream, a));
+                a.gh2_mask = cp->gh2_mask ? lane_mask_noise : nullptr;
+                LCHK(launch_row_split(g.Pw, mode, dim3(blocks, B), stream, a));
                 return 0;
             }
             LCHK(launch_row<R>(g.Pw, mode, dim3(blocks + (finalize ? 1 : 0), B), stream, a));
@@ -1586,21 +1518,19 @@ template <typename R> struct Engine : EngineBase {
         dil_lo = lo; dil_hi = hi; dil_valid = true;
         return 0;
     }
-    // the tile-resident fused column kernel applies: fp32, 4096 / 8192 rows, the SLM rows within six register slots
-    // (the kernel shifts its transform input by tile_shift() rows -- any multiple of 16 keeps the shift-theorem factor a
-    //  per-lane constant -- so the SLM rows start in the first 16 rows of register slot 0)
-    int tile_shift() const { return opt_tile_shift16 ? (g.r0 / 16) * 16 : (g.r0 / (g.Ph / 16)) * (g.Ph / 16); }
-    int tile_slots() const { const int Tc = g.Ph / 16; return (g.r0 - tile_shift() + g.Sh + Tc - 1) / Tc; }
-    bool tile_geometry_ok() const {
-        if (sizeof(R) != 4 || g.Ph < 4096 || !opt_tile) return false;
-        return tile_slots() <= 6;
+    // what plan_column_pass() reads, as far as it does not depend on the iteration: geometry, switches, the last column scan
+    PassFacts base_facts() const {
+        PassFacts f;
+        f.elem = (int)sizeof(R);
+        f.Ph = g.Ph; f.Pw = g.Pw; f.B = B; f.n_cu = n_cu; f.col_blocks = col_blocks; f.tile_blocks = tile_blocks; f.r0 = g.r0; f.Sh = g.Sh;
+        f.stat_groups = stat_ctx ? stat_ctx->groups : 0;
+        f.w_unit = w_unit;
+        f.sparse_tiles = sparse_tiles; f.sparse_dirty = sparse_dirty;
+        f.n_active_min = n_active_min; f.n_active_max = n_active_max; f.n_noise_max = n_noise_max; f.n_signal_max = n_signal_max;
+        f.tun = tun;
+        return f;
     }
-    // columns a workgroup pass of the column kernels handles side by side (ColCfg<N>::CPAR)
-    int col_cpar() const {
-        const int T = g.Ph / 16;
-        return T >= 256 ? 1 : std::min(4, 256 / T);
-    }
-    int list_blocks(int n_list) const { return std::max(1, std::min((n_list + col_cpar() - 1) / col_cpar(), n_cu * 3)); }
+    bool tile_geometry_ok() const { return hgs::tile_geometry_ok(base_facts()); }
     // (re)build the active-column list when weights or target changed since the last scan
     int refresh_sparse() {
         if (!sparse_dirty) return 0;
@@ -1620,7 +1550,7 @@ template <typename R> struct Engine : EngineBase {
         // rounded to whole tiles and that kernel walks the tile list: 45 ns per column against 80 for the per-column
         // kernel at 8192 points, and the row kernel moves whole 32-byte tile rows.
         sparse_tiles = false;
-        if (tile_geometry_ok() && opt_tile_list) {
+        if (tile_geometry_ok() && tun.tile_list) {
             std::vector<unsigned char> act((size_t)B * g.Pw);
             HIPCHK(hipMemcpyAsync(act.data(), col_active, act.size(), hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
@@ -1710,7 +1640,7 @@ template <typename R> struct Engine : EngineBase {
         a.wpartial = wpartial; a.fpartial = fpartial; a.tw = tw_col; a.scale = (R)(1.0 / std::sqrt((double)g.Ph));
         a.col_xmap = col_xmap;
         // float64, 4096 / 8192 rows: col_fused_kernel in its shifted form (the SLM rows in the first fnr register slots)
-        if (sizeof(R) == 8 && g.Ph >= 4096 && opt_fused_shift) {
+        if (sizeof(R) == 8 && g.Ph >= 4096 && tun.fused_shift) {
             const int sh = (g.r0 / 16) * 16, Tc = g.Ph / 16, nr = (g.r0 - sh + g.Sh + Tc - 1) / Tc;
             if (nr <= 6) { a.fshift = sh; a.fnr = nr; }
         }
@@ -1724,13 +1654,12 @@ template <typename R> struct Engine : EngineBase {
 
     int n2f(int store_pff) override {
         RoctxRange range(opt_roctx, "hgs_nearfield2farfield");
-        row_split = row_split_noise_only = false;       // (a single-pass MRAF call that failed between its column and row launch must not leak)
         if (cfg.kind == 1) return n2f_compressed(store_pff);
         if (general) return n2f_general(store_pff);
         if (int e = need_ff()) return e;
         if (store_pff) { if (int e = need_pff()) return e; }
         // (a fused loop that ended on its dense row launch left G of every column behind: the transform starts with its column pass)
-        if (!(opt_keep_g && gh_state == 0)) { if (int e = run_row(0, false)) return e; }
+        if (!(tun.keep_g && gh_state == 0)) { if (int e = run_row(0, false)) return e; }
         int r = timed(HGS_K_COL_FWD, [&]() -> int {
             ColArgs<R> a = col_args();
             a.store_pff = store_pff;
@@ -1746,7 +1675,6 @@ template <typename R> struct Engine : EngineBase {
 
     int f2n() override {
         RoctxRange range(opt_roctx, "hgs_farfield2nearfield");
-        row_split = row_split_noise_only = false;
         if (cfg.kind == 1) return f2n_compressed();
         if (general) return f2n_general(false);
         if (!ff || !farfield_valid) return fail(HGS_ERR_STATE, "no farfield to transform back");
@@ -1775,7 +1703,7 @@ template <typename R> struct Engine : EngineBase {
                 if (use_run()) return run_f2n(a);
                 if (c_degree <= 1) { dispatch_note(dispatch_site<KCf2nPix, R, 1>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 1>), grid, dim3(C_WG), 0, stream, a); }
                 else if (c_degree == 2) { dispatch_note(dispatch_site<KCf2nPix, R, 2>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 2>), grid, dim3(C_WG), 0, stream, a); }
-                else if (cfg.n_monomials <= C_MTAB && opt_mono_tab) { dispatch_note(dispatch_site<KCf2nPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 3>), grid, dim3(C_WG), 0, stream, a); }
+                else if (cfg.n_monomials <= C_MTAB && tun.mono_tab) { dispatch_note(dispatch_site<KCf2nPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 3>), grid, dim3(C_WG), 0, stream, a); }
                 else { dispatch_note(dispatch_site<KCf2nPix, R, 0>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 0>), grid, dim3(C_WG), 0, stream, a); }
                 HIPCHK(hipGetLastError());
                 return 0;
@@ -1818,7 +1746,6 @@ template <typename R> struct Engine : EngineBase {
     }
 
     // flag evolution of _gs_farfield_routines (:1552-1585); returns what this iteration must do
-    struct Plan { int do_update, use_fixed, store_phase; };
     Plan plan_iteration(hgs_step* st, uint8_t* hist_slot) {
         Plan p{0, 0, 0};
         // _update_stats ran before the routines: the history sees the flag as it is now (:1479)
@@ -1987,10 +1914,153 @@ template <typename R> struct Engine : EngineBase {
     // off).  Everything else of the farfield is exactly zero and is neither computed nor moved.
     bool spot_sparse_ok(const hgs_step* st) {
         if (cfg.kind != 0 || general || st->mraf_enabled || st->method == HGS_GS || st->feedback == HGS_FB_PIXEL) return false;
-        if (!opt_sparse || opt_stepwise) return false;
+        if (!tun.sparse || opt_stepwise) return false;
         if (refresh_sparse()) return false;
         return n_active_min > 0 && n_active_max * 4 <= g.Pw;
     }
+    // ---- executors of a ColumnPlan (column_plan.hpp: what is launched is decided there) ----
+    PassFacts pass_facts(const hgs_step* st, const Plan& p, bool sparse_enabled) const {
+        PassFacts f = base_facts();
+        f.it = p;
+        f.method = st->method; f.mraf_enabled = st->mraf_enabled; f.zero_mode = st->zero_mode;
+        f.sparse_enabled = sparse_enabled;
+        return f;
+    }
+    // amp_ff on the spot columns dilated by the integration window (col_kernel FWD|STORE over that list)
+    int launch_dilated_forward() {
+        return timed(HGS_K_COL_FWD, [&]() -> int {
+            ColArgs<R> a = col_args();
+            a.col_list = col_list_d;
+            a.n_active = n_active_d_dev;
+            LCHK(launch_col<R>(g.Ph, C_FWD | C_STORE, dim3(list_blocks(base_facts(), n_active_d_max), B), stream, a));
+            return 0;
+        });
+    }
+    // the buffers a plan lists; f / cp: re-planned once where the device cannot give the farfield buffer of the float64 split form
+    int acquire(ColumnPlan& cp, PassFacts& f) {
+        if (cp.need_ffb && !ffb_zeroed) {
+            if (!ffb) {
+                void* q = nullptr;
+                if (hipMalloc(&q, (size_t)B * g.Ph * g.Pw * sizeof(C)) == hipSuccess) ffb = static_cast<C*>(q);
+                else {
+                    (void)hipGetLastError();
+                    f.ffb_unavailable = true;
+                    cp = plan_column_pass(f);
+                }
+            }
+            if (cp.need_ffb) {
+                HIPCHK(hipMemsetAsync(ffb, 0, (size_t)B * g.Ph * g.Pw * sizeof(C), stream));
+                ffb_zeroed = true;
+            }
+        }
+        // (dpartial: sized like wpartial)
+        if (cp.need_dpartial && !dpartial) { if (dalloc(&dpartial, (size_t)B * std::max(std::max(col_blocks, tile_blocks), n_cu * 3))) return HGS_ERR_DEVICE; }
+        if (cp.need_gh2 && !gh2) { if (dalloc(&gh2, (size_t)B * g.Sh * g.Pw)) return HGS_ERR_DEVICE; }
+        if (cp.need_nog_dev && !nog_dev) { if (dalloc(&nog_dev, (size_t)B)) return HGS_ERR_DEVICE; }
+        return 0;
+    }
+    // the pre-pass of the single-inverse MRAF update (its own profile slot: a forward-only column launch)
+    int launch_prepass(const ColumnPlan& cp, const CParams<R>& cprm) {
+        if (!cp.presum && !cp.presum_col) return 0;
+        return timed(HGS_K_COL_FWD, [&]() -> int {
+            ColArgs<R> pa = col_args();
+            pa.cp = cprm;
+            pa.wpartial = dpartial;
+            const dim3 grid(cp.prepass_grid, B);
+            if (cp.presum_col) {             // per-column, over the signal columns
+                pa.cp.weights_only = 1;
+                pa.cp.presum = 1;
+                pa.col_list = col_list_signal;
+                pa.n_active = n_signal_dev;
+                pa.list_xmap = cp.prepass_list_xmap;
+                LCHK(launch_fused<R>(g.Ph, 0, grid, stream, pa));
+            } else if constexpr (sizeof(R) == 4) {
+                pa.col_flags = col_active;
+                pa.sig_rows = (g.lane_T > 0 && tun.presum_rows) ? sig_rows : nullptr;
+                LCHK(launch_presum(g.Ph, cp.prepass_nr, grid, stream, pa, cp.prepass_shift));
+            }
+            return 0;
+        });
+    }
+    int launch_family(const ColLaunch& l, const ColArgs<R>& a) {
+        const int N = g.Ph;
+        const dim3 grid(l.grid, B);
+        switch (l.family) {
+            case ColFamily::fused: return launch_fused<R>(N, l.phase_mode, grid, stream, a);
+            case ColFamily::fused_stats: return launch_fused_stats<R>(N, l.phase_mode, grid, stream, a);
+            case ColFamily::tile: return launch_tile<R>(N, l.phase_mode, grid, stream, a, l.shift);
+            case ColFamily::tile_stats: return launch_tile_stats<R>(N, l.phase_mode, grid, stream, a, l.shift);
+            case ColFamily::tile_extras: return launch_tile_extras<R>(N, l.phase_mode, grid, stream, a, l.shift);
+            case ColFamily::tile_extras_stats: return launch_tile_extras_stats<R>(N, l.phase_mode, grid, stream, a, l.shift);
+            default:            // the float32-only families (the plan names none of them for 8-byte elements)
+                if constexpr (sizeof(R) == 4) switch (l.family) {
+                    case ColFamily::fused_rule1: return launch_fused_rule1(N, l.phase_mode, grid, stream, a);
+                    case ColFamily::fused_rule2: return launch_fused_rule2(N, l.phase_mode, grid, stream, a);
+                    case ColFamily::tile_rule: return launch_tile_rule(N, l.phase_mode, l.rule, l.nr, grid, stream, a, l.shift);
+                    case ColFamily::tile_rule_listed: return launch_tile_rule_listed(N, l.phase_mode, l.rule, l.nr, grid, stream, a, l.shift);
+                    case ColFamily::tile_split: return launch_tile_split(N, l.phase_mode, l.nr, l.rule_ok, grid, stream, a, l.shift);
+                    case ColFamily::tile_split_stats: return launch_tile_split_stats(N, l.phase_mode, l.nr, l.rule_ok, grid, stream, a, l.shift);
+                    case ColFamily::tile_presum: return launch_tile_presum(N, l.phase_mode, l.nr, grid, stream, a, l.shift);
+                    case ColFamily::tile2: return launch_tile2(N, l.phase_mode, l.rule, l.nr, grid, stream, a, l.shift, l.half_xmap ? 1 : 0);
+                    default: break;
+                }
+                return (int)hipErrorInvalidValue;
+        }
+    }
+    // one launch of the column pass; then_scale: wscale = 1/||w'|| from its partials right after it (reduce_to_scale)
+    int launch_column(const ColLaunch& l, const CParams<R>& cprm, bool then_scale = false) {
+        return timed(HGS_K_COL_FUSED, [&]() -> int {
+            ColArgs<R> a = col_args();
+            a.cp = cprm;
+            a.cp.do_update = l.do_update;
+            a.cp.nog_pass = l.nog_pass ? 1 : 0;
+            a.cp.weights_only = l.weights_only ? 1 : 0;
+            if (l.use_nog) a.cp.nog = nog_dev;
+            if (l.split64) { a.cp.split = 1; a.ffb = ffb; }
+            if (l.n_dpartial) { a.dpartial = dpartial; a.n_dpartial = l.n_dpartial; }
+            if (l.stats) {
+                a.do_stats = l.stats;
+                a.spartial = stat_partial;
+                a.tsum = stat_tsum;
+                a.inv_fsum = 1.0 / amp_norm2;
+                // launches of different geometry share the partial buffer: reset the slots
+                hipLaunchKernelGGL(stat_fill_neutral, dim3((unsigned)((stat_nslots + 255) / 256)), dim3(256), 0, stream,
+                                   stat_partial, stat_nslots);
+            }
+            if (l.listed) { a.col_list = col_list; a.n_active = n_active_dev; }
+            a.list_xmap = l.list_xmap ? 1 : 0;
+            if (l.col_flags) a.col_flags = col_active;
+            a.few_active = l.few_active ? 1 : 0;
+            if (l.family == ColFamily::tile_split || l.family == ColFamily::tile_split_stats) { a.gh2 = gh2; a.gh2_sparse = l.gh2_sparse ? 1 : 0; }
+            LCHK(launch_family(l, a));
+            if (l.nog_pass) {
+                if (int e = reduce(wpartial, l.grid, sums + 1 * B)) return e;
+                hipLaunchKernelGGL(nog_finalize<R>, dim3((B + 63) / 64), dim3(64), 0, stream, (const double*)(sums + 1 * B),
+                                   l.listed ? (const int*)n_active_dev : (const int*)nullptr, g.Ph, g.Pw, nog_dev, B);
+                HIPCHK(hipGetLastError());
+            }
+            if (then_scale) {
+                hipLaunchKernelGGL(reduce_to_scale<R>, dim3(B), dim3(256), 0, stream, (const double*)wpartial, l.grid,
+                                   sums + 2 * B, wscale);
+                HIPCHK(hipGetLastError());
+            }
+            return 0;
+        });
+    }
+    // float64 split: the noise part, farfield values -> gh2, noise columns only (own profile slot)
+    int launch_noise_inverse(const ColumnPlan& cp) {
+        if (!cp.noise_inverse_grid) return 0;
+        return timed(HGS_K_COL_INV, [&]() -> int {
+            ColArgs<R> nb = col_args();
+            nb.ff = ffb;
+            nb.gh = gh2;
+            nb.col_list = col_list_noise;
+            nb.n_active = n_noise_dev;
+            LCHK(launch_col<R>(g.Ph, C_LOAD | C_INV, dim3(cp.noise_inverse_grid, B), stream, nb));
+            return 0;
+        });
+    }
+
     int iterate_spot_sparse(hgs_step* st, int n, uint8_t* hist) {
         if (int e = normalize_weights_now()) return e;      // the N-vector rule keeps the weights normalised
         if (int e = need_ff()) return e;
@@ -2013,23 +2083,14 @@ template <typename R> struct Engine : EngineBase {
         for (int i = 0; i < n; ++i) {
             gh_state = -1;
             if (p.use_fixed || p.store_phase) { if (int e = need_pff()) return e; }
-            const CParams<R> cp = cparams(st, p);
-            if (windows_needed(p)) {
-                int r = timed(HGS_K_COL_FWD, [&]() -> int {
-                    ColArgs<R> a = col_args();
-                    a.col_list = col_list_d;
-                    a.n_active = n_active_d_dev;
-                    LCHK(launch_col<R>(g.Ph, C_FWD | C_STORE, dim3(list_blocks(n_active_d_max), B), stream, a));
-                    return 0;
-                });
-                if (r) return r;
-            }
+            const CParams<R> cprm = cparams(st, p);
+            if (windows_needed(p)) { if (int e = launch_dilated_forward()) return e; }
             if (p.do_update) {
                 int r = timed(HGS_K_ELEMENTWISE, [&]() -> int {
                     SpotArgs<R> sa{};
                     sa.g = g; sa.n_spots = cfg.n_spots; sa.width = st->spot_window; sa.feedback = st->feedback;
                     sa.spot_xy = spot_xy; sa.amp_ff = aff; sa.ext_amp = ext_amp; sa.spot_amp = spot_amp; sa.w = w;
-                    sa.fb = spot_fb; sa.cp = cp;
+                    sa.fb = spot_fb; sa.cp = cprm;
                     sa.inline_window = 1;
                     hipLaunchKernelGGL(spot_update<R>, dim3(B), dim3(256), 0, stream, sa);
                     HIPCHK(hipGetLastError());
@@ -2037,30 +2098,9 @@ template <typename R> struct Engine : EngineBase {
                 });
                 if (r) return r;
             }
-            int r = timed(HGS_K_COL_FUSED, [&]() -> int {
-                ColArgs<R> a = col_args();
-                a.cp = cp;
-                a.cp.do_update = 0;                          // the weights were updated above
-                a.col_list = col_list;
-                a.n_active = n_active_dev;
-                const int blocks = list_blocks(n_active_max);
-                wpartial_n = blocks;
-                const int phase_mode = p.use_fixed ? 2 : (p.store_phase ? 1 : 0);
-                if (groups & 1) {
-                    a.do_stats = 1;
-                    a.spartial = stat_partial;
-                    a.tsum = stat_tsum;
-                    a.inv_fsum = 1.0 / amp_norm2;
-                    hipLaunchKernelGGL(stat_fill_neutral, dim3((unsigned)((stat_nslots + 255) / 256)), dim3(256), 0, stream,
-                                       stat_partial, stat_nslots);
-                    LCHK(launch_fused_stats<R>(g.Ph, phase_mode, dim3(blocks, B), stream, a));
-                } else {
-                    LCHK(fused_launch(phase_mode, dim3(blocks, B), a));
-                }
-                return 0;
-            });
-            if (r) return r;
-            if (stat_ctx) { if (int e = fused_stats_finish(i)) return e; }
+            const ColumnPlan cp = plan_spot_sparse_pass(pass_facts(st, p, true));      // (the weights were updated above)
+            if (int e = launch_column(cp.main, cprm)) return e;
+            if (stat_ctx) { if (int e = fused_stats_finish(i, cp)) return e; }
             if (p.store_phase) have_pff = true;
             if (stat_ctx) { if (int e = eff_gate_after(st, nullptr, stat_ctx->dev_out + ((size_t)i * 2 + st->efficiency_group) * B * 4)) return e; }
             st->iter++;
@@ -2070,8 +2110,8 @@ template <typename R> struct Engine : EngineBase {
                 pn = plan_iteration(st, hist ? hist + i + 1 : nullptr);
                 store_next = windows_needed(pn) ? 2 : 1;
             }
-            const int last_mode = (opt_keep_g && sizeof(R) == 4) ? 3 : 1;          // (MODE 3 stores every column, see iterate())
-            if (int e = run_row(i + 1 < n ? 2 : last_mode, false, 1, i + 1 < n ? store_next : (last_mode == 3 ? 0 : store_next))) return e;
+            const bool last = i + 1 == n;
+            if (int e = run_row(last ? cp.last_mode : 2, false, 1, (last && cp.last_mode == 3) ? 0 : store_next, &cp)) return e;
             p = pn;
         }
         return 0;
@@ -2079,7 +2119,6 @@ template <typename R> struct Engine : EngineBase {
 
     int iterate(hgs_step* st, int n, uint8_t* hist) override {
         RoctxRange range(opt_roctx, "hgs_iterate");
-        row_split = row_split_noise_only = false;
         if (n < 0) return fail(HGS_ERR_ARG, "n_iter must be >= 0");
         if (n == 0) return 0;
         if (int e = check_step(st)) return e;
@@ -2104,15 +2143,15 @@ template <typename R> struct Engine : EngineBase {
         // transformed (col_fused_kernel with a column list) and only they cross HBM between the two
         // kernels.  phase_ff (WGS-Kim) is then stored on the active columns only: nothing else can be
         // read back by the loop.
-        bool sparse_enabled = false;
-        if (opt_sparse) {
+        bool sp = false;
+        if (tun.sparse) {
             if (int e = refresh_sparse()) return e;
-            sparse_enabled = n_active_min > 0 && n_active_max * 2 <= g.Pw;
-        } else if (st->mraf_enabled && st->method != HGS_GS && opt_mraf_split && opt_gh2_mask && tile_geometry_ok() && g.Pw >= 4096) {
+            sp = n_active_min > 0 && n_active_max * 2 <= g.Pw;
+        } else if (st->mraf_enabled && st->method != HGS_GS && tun.mraf_split && tun.gh2_mask && tile_geometry_ok() && g.Pw >= 4096) {
             // single-pass MRAF: which columns hold a NaN target (the noise part exists only there) -- a fact about the
             // target, scanned once per upload; the dense launches themselves still walk every column
             if (int e = refresh_sparse()) return e;
-        } else if (sizeof(R) == 4 && g.Ph == 4096 && B == 1 && opt_tile2) {
+        } else if (sizeof(R) == 4 && g.Ph == 4096 && B == 1 && tun.tile2) {
             // dense launches of one hologram at 4096 rows: how many columns hold anything picks the instance of the half-width
             // tile kernel (ColArgs::few_active) -- a fact about the target, scanned once per upload
             if (int e = refresh_sparse()) return e;
@@ -2120,7 +2159,7 @@ template <typename R> struct Engine : EngineBase {
         // "computational_spot" statistics on the sparse path: amp_ff is produced on the spot columns dilated
         // by the integration window (col_kernel FWD|STORE over that list) before the fused kernel runs
         const bool spot_stats = stat_ctx && (stat_ctx->groups & 2);
-        if (sparse_enabled && spot_stats) {
+        if (sp && spot_stats) {
             // windows sit at floor(spot_knm) (analysis.take, quirk A18), the weights at rint(spot_knm): one more
             // column to the left
             const int lo = (int)std::floor(-(stat_ctx->width - 1) / 2.0);
@@ -2129,277 +2168,40 @@ template <typename R> struct Engine : EngineBase {
         }
         const int store_sparse = spot_stats ? 2 : 1;
         Plan p = plan_iteration(st, hist ? hist : nullptr);
-        const bool sp = sparse_enabled;
         if (int e = keep_prev_phase(p, n)) return e;
         // (the previous call may have left G of these columns behind: gh_state, row_kernel MODE 3)
         if (!gh_holds(sp ? store_sparse : 0)) { if (int e = run_row(0, false, 0, sp ? store_sparse : 0)) return e; }
         for (int i = 0; i < n; ++i) {
             gh_state = -1;          // the column pass turns G into H in place
             if (p.use_fixed || p.store_phase) { if (int e = need_pff()) return e; }
-            // MRAF with a weight update takes two passes over the columns: the rebuilt field mixes the
-            // NORMALISED weights (signal region) with the un-weighted farfield (noise region), so ||w'|| has
-            // to be known first.  Pass 0: forward transform + weight update (+ statistics), no inverse;
-            // then wscale = 1/||w'||; pass 1: forward transform again, rebuild, inverse.
-            const bool two_pass = st->mraf_enabled && p.do_update;
-            // ... unless the tile-resident kernel runs the column pass: the inverse transform is linear, so it transforms the
-            // signal part (un-normalised new weights) and the noise part separately in ONE pass and the row kernel joins
-            // them once ||w'|| is known (col_tile_kernel RULE 3, row_kernel SPLIT)
-            const int m0 = tile_shift(), m1 = m0 + tile_slots() - 1;   // (m0: row shift; m1 - m0 + 1 = slots of the load layout the SLM rows occupy)
-            const bool tile_path = (!sp || sparse_tiles) && tile_geometry_ok();
-            // (a column list rounded to whole tiles: the same kernels walk the list)
-            const int tile_grid = sp ? std::max(1, std::min(tile_blocks, n_active_max / 4)) : tile_blocks;
-            const bool split = two_pass && tile_path && g.Pw >= 4096 && opt_mraf_split;
-            // ... and the float64 per-column kernel the same way, its noise part through a farfield buffer and an inverse-only
-            // launch over the columns that hold noise (CParams::split): one forward transform and one read of weights and
-            // target per column instead of two
-            // (float32 too where the tile-resident kernel does not run: SLM rows over more than six register slots, short columns)
-            const bool split64_ok = two_pass && !tile_path && g.Pw >= 4096 && opt_mraf_split && opt_mraf_split64;
-            // (a column list: only where at most half of the listed columns hold noise -- where every one does, as around a noise
-            //  box, the single pass saves no transform and pays the extra launch: measured 119 against 105 us at 4096^2)
-            // (not where the single-inverse form below takes the update: presum_ok)
-            const bool presum_ok = two_pass && opt_mraf_presum && w_unit && !stat_ctx &&
-                                   (st->method == HGS_WGS_LEONARDO || st->method == HGS_WGS_KIM);
-            bool split64 = split64_ok && !presum_ok;
-            if (split64) {
-                if (int e = refresh_noise()) return e;
-                if (sp && n_noise_max * 2 > n_active_max) split64 = false;
-            }
-            if (split64 && !ffb_zeroed) {
-                // (a farfield-sized buffer more: 268 MB per float64 hologram at 4096^2.  Where the device cannot give it the
-                //  update runs in two passes as it did before round 4 -- slower, same results -- instead of failing the call)
-                if (!ffb) {
-                    void* p = nullptr;
-                    if (hipMalloc(&p, (size_t)B * g.Ph * g.Pw * sizeof(C)) != hipSuccess) { (void)hipGetLastError(); split64 = false; }
-                    else ffb = static_cast<C*>(p);
-                }
-                if (split64) {
-                    HIPCHK(hipMemsetAsync(ffb, 0, (size_t)B * g.Ph * g.Pw * sizeof(C), stream));
-                    ffb_zeroed = true;
-                }
-            }
-            // ... and with ONE inverse per column where ||w'|| can be had BEFORE the field is rebuilt (round 6): the weights that
-            // enter this update are normalised (w_unit), so ||w'||^2 = 1 + D, D = sum over the signal pixels of w'^2 - w^2, which a
-            // forward-only pre-pass over the columns that hold signal pixels forms (col_presum_kernel; a quarter of the columns
-            // at cfg 5).  The main pass (col_tile_kernel RULE 5) rebuilds with the final scale: no second inverse in the noise
-            // columns, no noise part parked in LDS, nothing for the row kernel to join.  WGS-Leonardo / WGS-Kim without in-pass
-            // statistics; the first update after new weights or a new target (and every other rule) takes the split form.
-            const bool presum = presum_ok && split && sizeof(R) == 4;
-            // ... and everywhere else the fused path runs an MRAF update (float64; float32 geometries outside the tile-resident
-            // kernel's or narrower than 4096 columns): the per-column kernel makes the pre-pass over the list of signal columns
-            // (CParams::presum) and the main pass -- per-column or the generic tile kernel -- rebuilds with the pre-summed scale.
-            // Replaces the float64 split form (pass + inverse-only launch over the noise columns + joining row launch) and the
-            // two-pass form.
-            bool presum_col = presum_ok && !presum;
-            if (presum_col) {
-                if (int e = refresh_signal()) return e;
-                if (n_signal_max <= 0) presum_col = false;
-                else if (!dpartial) { if (dalloc(&dpartial, (size_t)B * std::max(std::max(col_blocks, tile_blocks), n_cu * 3))) return HGS_ERR_DEVICE; }
-            }
-            // (a target without a single finite non-zero pixel: D = 0 trivially, but nothing to gain either -- two plain passes)
-            // (the pre-pass' grid: one workgroup per CU slot it can hold)
-            const int presum_blocks = std::max(1, std::min(g.Pw / 4, (env_presum_blocks > 0 ? std::min(env_presum_blocks, 3 * n_cu)
-                                                                         : (g.Ph >= 8192 ? 1 : 2) * n_cu) / B));
-            if (presum) {
-                if (int e = refresh_sparse()) return e;         // the column flags (clean unless the weights / target moved)
-                if (!dpartial) { if (dalloc(&dpartial, (size_t)B * std::max(std::max(col_blocks, tile_blocks), n_cu * 3))) return HGS_ERR_DEVICE; }
-            }
-            const bool split_any = split || split64;
-            if (split_any && !presum && !gh2) { if (dalloc(&gh2, (size_t)B * g.Sh * g.Pw)) return HGS_ERR_DEVICE; }
-            // WGS-Nogrette needs nanmean(feedback / target) over the whole farfield before the update (:1851):
-            // one more forward-only pass that just accumulates it
-            const bool nog = st->method == HGS_WGS_NOGRETTE && p.do_update;
-            if (nog && !nog_dev) { if (dalloc(&nog_dev, (size_t)B)) return HGS_ERR_DEVICE; }
-            int r = 0;
-            if (sp && spot_stats) {
-                r = timed(HGS_K_COL_FWD, [&]() -> int {
-                    ColArgs<R> a = col_args();
-                    a.col_list = col_list_d;
-                    a.n_active = n_active_d_dev;
-                    LCHK(launch_col<R>(g.Ph, C_FWD | C_STORE, dim3(list_blocks(n_active_d_max), B), stream, a));
-                    return 0;
-                });
-                if (r) return r;
-            }
-            if (presum) {                 // the pre-pass (its own profile slot: a forward-only column launch)
-                r = timed(HGS_K_COL_FWD, [&]() -> int {
-                    ColArgs<R> pa = col_args();
-                    pa.cp = cparams(st, p);
-                    pa.col_flags = col_active;
-                    pa.sig_rows = (g.lane_T > 0 && opt_presum_rows) ? sig_rows : nullptr;
-                    pa.wpartial = dpartial;
-                    LCHK(presum_launch(g.Ph, m1 - m0 + 1, dim3(presum_blocks, B), stream, pa, m0));
-                    return 0;
-                });
-                if (r) return r;
-            }
-            int presum_col_blocks = 0;
-            if (presum_col) {             // the per-column pre-pass over the signal columns
-                r = timed(HGS_K_COL_FWD, [&]() -> int {
-                    ColArgs<R> pa = col_args();
-                    pa.cp = cparams(st, p);
-                    pa.cp.weights_only = 1;
-                    pa.cp.presum = 1;
-                    pa.col_list = col_list_signal;
-                    pa.n_active = n_signal_dev;
-                    pa.wpartial = dpartial;
-                    // (no more workgroups than the dense launch of this geometry keeps resident: at 8192 rows in float64 one per CU --
-                    //  the list over three rounds of workgroups cost the pre-pass a prologue per round)
-                    presum_col_blocks = std::max(1, std::min(list_blocks(n_signal_max), env_presum_blocks > 0 ? env_presum_blocks : col_blocks));
-                    // (fewer than four columns per workgroup pass: the groups of a 4-column run of the list on one XCD, as for
-                    //  the column-list launches of the loop -- the signal columns of an image fill their tiles)
-                    const int gp = 8 * (4 / col_cpar());
-                    if (list_xmap && col_cpar() < 4 && presum_col_blocks >= gp) {
-                        presum_col_blocks -= presum_col_blocks % gp;
-                        pa.list_xmap = 1;
-                    }
-                    LCHK(launch_fused<R>(g.Ph, 0, dim3(presum_col_blocks, B), stream, pa));
-                    return 0;
-                });
-                if (r) return r;
-            }
-            for (int pass = nog ? -1 : 0; pass < (two_pass && !split_any && !presum_col ? 2 : 1) && !r; ++pass) {
-                r = timed(HGS_K_COL_FUSED, [&]() -> int {
-                    ColArgs<R> a = col_args();
-                    a.cp = cparams(st, p);
-                    int phase_mode = p.use_fixed ? 2 : (p.store_phase ? 1 : 0);
-                    if (pass == -1) {                 // Nogrette: sum of fc only
-                        a.cp.nog_pass = 1;
-                        a.cp.weights_only = 1;
-                        phase_mode = 0;
-                    } else if (nog) {
-                        a.cp.nog = nog_dev;
-                    }
-                    if (two_pass && !split_any && !presum_col && pass == 0) {
-                        a.cp.weights_only = 1;
-                        phase_mode = 0;
-                    }
-                    if (presum_col) {
-                        a.dpartial = dpartial;
-                        a.n_dpartial = presum_col_blocks;
-                    }
-                    if (split64 && pass == 0) {
-                        a.cp.split = 1;
-                        a.ffb = ffb;
-                        row_split = row_split_noise_only = true;
-                    }
-                    if (two_pass && pass == 1) a.cp.do_update = 0;
-                    if (stat_ctx && pass == 0 && (!sp || (stat_ctx->groups & 1))) {
-                        a.do_stats = sp ? (stat_ctx->groups & 1) : stat_ctx->groups;   // sparse: amp_ff already stored
-                        a.spartial = stat_partial;
-                        a.tsum = stat_tsum;
-                        a.inv_fsum = 1.0 / amp_norm2;
-                        // launches of different geometry share the partial buffer: reset the slots
-                        hipLaunchKernelGGL(stat_fill_neutral, dim3((unsigned)((stat_nslots + 255) / 256)), dim3(256), 0, stream,
-                                           stat_partial, stat_nslots);
-                    }
-                    wpartial_n = col_blocks;
-                    if (sp) {
-                        a.col_list = col_list;
-                        a.n_active = n_active_dev;
-                    }
-                    if (sp && !tile_path) {
-                        int blocks = list_blocks(n_active_max);
-                        // fewer than four columns per workgroup pass: the groups of a 4-column run of the list on one XCD
-                        // (they share 32-byte tile rows where the active set is dense; ColArgs::list_xmap)
-                        const int gp = 8 * (4 / col_cpar());
-                        if (list_xmap && col_cpar() < 4 && blocks >= gp) {
-                            blocks -= blocks % gp;
-                            a.list_xmap = 1;
-                        }
-                        wpartial_n = blocks;
-                        if (a.do_stats) LCHK(launch_fused_stats<R>(g.Ph, phase_mode, dim3(blocks, B), stream, a));
-                        else LCHK(fused_launch(phase_mode, dim3(blocks, B), a));
-                    } else if (presum && pass == 0) {
-                        wpartial_n = tile_grid;
-                        a.dpartial = dpartial;
-                        a.n_dpartial = presum_blocks;
-                        if (sp) a.col_flags = col_active;
-                        LCHK(tile_presum(g.Ph, phase_mode, m1 - m0 + 1, dim3(tile_grid, B), stream, a, m0));
-                    } else if (split && pass == 0) {
-                        wpartial_n = tile_grid;
-                        a.gh2 = gh2;
-                        a.gh2_sparse = (opt_gh2_mask && !sparse_dirty && !sp) ? 1 : 0;   // (set together with RowArgs::gh2_mask below)
-                        if (sp) a.col_flags = col_active;       // (scanned with the weights / target this loop started from)
-                        LCHK(tile_split(g.Ph, phase_mode, m1 - m0 + 1, opt_tile_rule, dim3(tile_grid, B), stream, a, m0));
-                        row_split = true;
-                    } else if (int t2 = tile2_grid(sp, tile_path, a, phase_mode)) {
-                        // half-width tile-resident kernel: batches at 4096 rows (three workgroups per CU), dense launches at
-                        // 2048 rows (col_tile2_kernel); plain passes only
-                        wpartial_n = t2;
-                        a.few_active = (!sparse_dirty && n_active_min > 0 && n_active_max * 4 <= g.Pw) ? 1 : 0;
-                        LCHK(tile2_launch(g.Ph, phase_mode, a.cp.do_update ? 1 : 2, m1 - m0 + 1, dim3(t2, B), stream, a, m0,
-                                          (g.Ph >= 4096 && t2 % 16 == 0) ? 1 : 0));
-                    } else if (tile_path) {
-                        wpartial_n = tile_grid;
-                        const bool extras = a.cp.mraf || a.cp.nog_pass || a.cp.weights_only;
-                        // MRAF without a weight update (GS, iteration 0, the no-update bodies of WGS): the rule-free MRAF form
-                        // compiled per slot count (col_tile_kernel RULE 6) instead of the generic six-slot instance
-                        const bool mraf_plain = a.cp.mraf && !a.cp.do_update && !a.cp.nog_pass && !a.cp.weights_only &&
-                                                !a.do_stats && opt_tile_rule && opt_mraf_presum && sizeof(R) == 4 && !a.cp.zero_mode;
-                        if (mraf_plain) {
-                            if (sp) a.col_flags = col_active;
-                            LCHK(tile_presum(g.Ph, phase_mode, m1 - m0 + 1, dim3(tile_grid, B), stream, a, m0));
-                        } else
-                        if (extras) {
-                            if (a.do_stats) LCHK(launch_tile_extras_stats<R>(g.Ph, phase_mode, dim3(tile_grid, B), stream, a, m0));
-                            else LCHK(launch_tile_extras<R>(g.Ph, phase_mode, dim3(tile_grid, B), stream, a, m0));
-                        } else {
-                            // the hot launches: weight rule compiled in (col_tile_kernel RULE) where it is the
-                            // Leonardo / Kim update or no update at all
-                            const int rule = !opt_tile_rule ? 0 : !a.cp.do_update ? 2
-                                             : (a.cp.method == HGS_WGS_LEONARDO || a.cp.method == HGS_WGS_KIM) ? 1 : 0;
-                            if (a.do_stats) LCHK(launch_tile_stats<R>(g.Ph, phase_mode, dim3(tile_grid, B), stream, a, m0));
-                            else if (rule != 0) LCHK(tile_rule(g.Ph, phase_mode, rule, opt_tile_nr4 ? m1 - m0 + 1 : 6, dim3(tile_grid, B), stream, a, m0));
-                            else LCHK(launch_tile<R>(g.Ph, phase_mode, dim3(tile_grid, B), stream, a, m0));
-                        }
-                    } else {
-                        if (a.do_stats) LCHK(launch_fused_stats<R>(g.Ph, phase_mode, dim3(col_blocks, B), stream, a));
-                        else LCHK(fused_launch(phase_mode, dim3(col_blocks, B), a));
-                    }
-                    if (pass == -1) {
-                        if (int e = reduce(wpartial, wpartial_n, sums + 1 * B)) return e;
-                        hipLaunchKernelGGL(nog_finalize<R>, dim3((B + 63) / 64), dim3(64), 0, stream, (const double*)(sums + 1 * B),
-                                           sp ? (const int*)n_active_dev : (const int*)nullptr, g.Ph, g.Pw, nog_dev, B);
-                        HIPCHK(hipGetLastError());
-                    }
-                    // (the single-inverse pass needs wscale only from the NEXT column launch on: the row launch below folds the
-                    //  partials, as after a plain update -- one 4.7 us launch less per iteration)
-                    if (two_pass && pass == 0 && !presum && !presum_col) {
-                        hipLaunchKernelGGL(reduce_to_scale<R>, dim3(B), dim3(256), 0, stream, (const double*)wpartial, wpartial_n,
-                                           sums + 2 * B, wscale);
-                        HIPCHK(hipGetLastError());
-                    }
-                    return 0;
-                });
-            }
-            if (r) return r;
-            if (split64 && n_noise_max > 0) {        // the noise part: farfield values -> gh2, noise columns only (own profile slot)
-                r = timed(HGS_K_COL_INV, [&]() -> int {
-                    ColArgs<R> nb = col_args();
-                    nb.ff = ffb;
-                    nb.gh = gh2;
-                    nb.col_list = col_list_noise;
-                    nb.n_active = n_noise_dev;
-                    LCHK(launch_col<R>(g.Ph, C_LOAD | C_INV, dim3(list_blocks(n_noise_max), B), stream, nb));
-                    return 0;
-                });
-                if (r) return r;
-            }
-            if (stat_ctx) { if (int e = fused_stats_finish(i)) return e; }
+            // facts -> plan: the column scans the form consults first (their counts feed the choice), then the plan itself
+            PassFacts f = pass_facts(st, p, sp);
+            const Scans scans = scans_needed(f);
+            if (scans.noise) { if (int e = refresh_noise()) return e; }
+            if (scans.signal) { if (int e = refresh_signal()) return e; }
+            if (scans.flags) { if (int e = refresh_sparse()) return e; }         // (clean unless the weights / target moved)
+            if (scans.noise || scans.signal || scans.flags) f = pass_facts(st, p, sp);
+            ColumnPlan cp = plan_column_pass(f);
+            if (int e = acquire(cp, f)) return e;
+            // execute
+            const CParams<R> cprm = cparams(st, p);
+            if (cp.dilated_forward) { if (int e = launch_dilated_forward()) return e; }
+            if (int e = launch_prepass(cp, cprm)) return e;
+            if (cp.nog) { if (int e = launch_column(cp.nog_pass, cprm)) return e; }
+            if (int e = launch_column(cp.main, cprm, cp.scale_after_main)) return e;
+            if (cp.second_pass) { if (int e = launch_column(cp.second, cprm)) return e; }
+            if (int e = launch_noise_inverse(cp)) return e;
+            if (stat_ctx) { if (int e = fused_stats_finish(i, cp)) return e; }
             if (p.store_phase) have_pff = true;
-            if (p.do_update) { w_pending = true; w_unit = true; }       // (wscale: from this pass' partials, here or in the row launch below)
+            if (p.do_update) { w_pending = true; w_unit = true; }       // (wscale: from this pass' partials, in the pass or in the row launch below)
             if (stat_ctx) { if (int e = eff_gate_after(st, nullptr, stat_ctx->dev_out + ((size_t)i * 2 + st->efficiency_group) * B * 4)) return e; }
             st->iter++;
             Plan pn{0, 0, 0};
             if (i + 1 < n) pn = plan_iteration(st, hist ? hist + i + 1 : nullptr);
-            // the row kernel that follows folds the weight-norm partials into wscale (unless already done);
-            // on the sparse path it reads the active columns and writes those the next column launches read
-            // the last launch of the call extracts the phase; in float32 (and unless a single-pass MRAF body has to join its
-            // two parts) it also leaves G of the next body behind (MODE 3) -- of EVERY column, also on the column-list path,
-            // so that whatever comes next (another call, the transform that ends optimize()) can start from it on every path
-            const int last_mode = (opt_keep_g && sizeof(R) == 4 && !row_split) ? 3 : 1;
+            // the row launch that closes the iteration: on the sparse path it reads the active columns and writes those the
+            // next column launches read; the last one of the call extracts the phase (cp.last_mode)
             const bool last = i + 1 == n;
-            if (int e = run_row(last ? last_mode : 2, p.do_update != 0 && (!two_pass || presum || presum_col), sp ? 1 : 0, (last && last_mode == 3) ? 0 : (sp ? store_sparse : 0)))
+            if (int e = run_row(last ? cp.last_mode : 2, cp.finalize, sp ? 1 : 0, (last && cp.last_mode == 3) ? 0 : (sp ? store_sparse : 0), &cp))
                 return e;
             p = pn;
         }
@@ -2410,9 +2212,9 @@ template <typename R> struct Engine : EngineBase {
     // Fused path: the column kernel accumulates the "computational" statistics of the field it
     // constrains (StatAcc) and, for the spot group, stores amp_ff for the window sums; one tiny
     // finalize launch per iteration; the host reads all n_iter results once at the end.
-    int fused_stats_finish(int i) {
+    int fused_stats_finish(int i, const ColumnPlan& cp) {
         StatCtx& c = *stat_ctx;
-        const int nparts = wpartial_n * STAT_WAVES;
+        const int nparts = cp.wpartial_n * STAT_WAVES;
         if (c.groups & 1) {
             hipLaunchKernelGGL(stat_finalize, dim3(B), dim3(256), 0, stream, (const double*)stat_partial, nparts,
                                (const double*)stat_tsum, 1.0 / amp_norm2, c.dev_out + ((size_t)i * 2 + 0) * B * 4);
@@ -2644,9 +2446,9 @@ template <typename R> struct Engine : EngineBase {
         // (a change of the column policy may change which columns the next launch expects in gh)
         if (option == HGS_OPT_SPARSE_COLUMNS || option == HGS_OPT_FORCE_STEPWISE || option == HGS_OPT_TILE_KERNEL) gh_state = -1;
         switch (option) {
-            case HGS_OPT_SPARSE_COLUMNS: opt_sparse = value ? 1 : 0; return 0;
+            case HGS_OPT_SPARSE_COLUMNS: tun.sparse = value ? 1 : 0; return 0;
             case HGS_OPT_FORCE_STEPWISE: opt_stepwise = value ? 1 : 0; return 0;
-            case HGS_OPT_TILE_KERNEL: opt_tile = value ? 1 : 0; sparse_dirty = true; return 0;
+            case HGS_OPT_TILE_KERNEL: tun.tile = value ? 1 : 0; sparse_dirty = true; return 0;
             case HGS_OPT_SEPARABLE: opt_separable = value ? 1 : 0; return 0;
             case HGS_OPT_SEPARABLE_MIN_SPOTS: opt_sep_min = value > 0 ? value : 1; return 0;
             case HGS_OPT_RUN_KERNELS: opt_run = value ? 1 : 0; return 0;
