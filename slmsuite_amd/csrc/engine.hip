@@ -1033,19 +1033,23 @@ template <typename R> struct Engine : EngineBase {
         farfield_valid = true;
         return 0;
     }
+    // the per-pixel compressed inverse, by polynomial degree (3: the monomial table; 0: any degree)
+    int pix_f2n(const CArgs<R>& a) {
+        const dim3 grid(c_nblocks, B);
+        if (c_degree <= 1) { dispatch_note(dispatch_site<KCf2nPix, R, 1>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 1>), grid, dim3(C_WG), 0, stream, a); }
+        else if (c_degree == 2) { dispatch_note(dispatch_site<KCf2nPix, R, 2>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 2>), grid, dim3(C_WG), 0, stream, a); }
+        else if (cfg.n_monomials <= C_MTAB && tun.mono_tab) { dispatch_note(dispatch_site<KCf2nPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 3>), grid, dim3(C_WG), 0, stream, a); }
+        else { dispatch_note(dispatch_site<KCf2nPix, R, 0>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 0>), grid, dim3(C_WG), 0, stream, a); }
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
     int f2n_compressed() {
         if (!ff || !farfield_valid) return fail(HGS_ERR_STATE, "no farfield to transform back");
         int r = timed(HGS_K_COL_INV, [&]() -> int {
             if (use_sep()) return sep_f2n(nullptr);
             CArgs<R> a = cargs();
-            const dim3 grid(c_nblocks, B);
             if (use_run()) return run_f2n(a);
-            if (c_degree <= 1) { dispatch_note(dispatch_site<KCf2nPix, R, 1>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 1>), grid, dim3(C_WG), 0, stream, a); }
-            else if (c_degree == 2) { dispatch_note(dispatch_site<KCf2nPix, R, 2>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 2>), grid, dim3(C_WG), 0, stream, a); }
-            else if (cfg.n_monomials <= C_MTAB && tun.mono_tab) { dispatch_note(dispatch_site<KCf2nPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 3>), grid, dim3(C_WG), 0, stream, a); }
-            else { dispatch_note(dispatch_site<KCf2nPix, R, 0>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 0>), grid, dim3(C_WG), 0, stream, a); }
-            HIPCHK(hipGetLastError());
-            return 0;
+            return pix_f2n(a);
         });
         farfield_valid = false;
         return r;
@@ -1699,14 +1703,8 @@ template <typename R> struct Engine : EngineBase {
                 if (use_sep()) return sep_f2n(nfbuf);
                 CArgs<R> a = cargs();
                 a.nf_out = nfbuf;
-                const dim3 grid(c_nblocks, B);
                 if (use_run()) return run_f2n(a);
-                if (c_degree <= 1) { dispatch_note(dispatch_site<KCf2nPix, R, 1>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 1>), grid, dim3(C_WG), 0, stream, a); }
-                else if (c_degree == 2) { dispatch_note(dispatch_site<KCf2nPix, R, 2>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 2>), grid, dim3(C_WG), 0, stream, a); }
-                else if (cfg.n_monomials <= C_MTAB && tun.mono_tab) { dispatch_note(dispatch_site<KCf2nPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 3>), grid, dim3(C_WG), 0, stream, a); }
-                else { dispatch_note(dispatch_site<KCf2nPix, R, 0>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 0>), grid, dim3(C_WG), 0, stream, a); }
-                HIPCHK(hipGetLastError());
-                return 0;
+                return pix_f2n(a);
             });
             farfield_valid = false;
             return r;

@@ -32,11 +32,6 @@
 #ifndef HGS_ABL_TRANS
 #define HGS_ABL_TRANS 0
 #endif
-// Wave-priority experiments (A/B builds): 0 none; 1 static, by the parity of the hardware wave slot (the two waves
-// sharing a SIMD get different priorities); 2 raised around the butterflies, lowered around the exchanges
-#ifndef HGS_PRIO
-#define HGS_PRIO 0
-#endif
 // Timeline instrumentation for tools/microbench/trace.hip: lane 0 of every wave stamps s_memtime at phase
 // boundaries into dynamic LDS at byte offset HGS_TRACE_OFF (128 events per wave); 0 in the product build.
 #ifndef HGS_TRACE
@@ -413,9 +408,6 @@ template <int N> constexpr int lds_elems() { return N == 8192 ? 2 * (16 * 272 + 
 //                   many transforms per workgroup (the column kernels).
 // RESIDENT = false: they are fetched from the (L1/L2-resident) table right before each use, which
 //                   frees ~24 VGPRs -- for kernels that are occupancy-bound (the row kernels).
-#ifndef HGS_WAVE_LOCAL_BARRIER
-#define HGS_WAVE_LOCAL_BARRIER 1
-#endif
 template <typename R, int N, bool RESIDENT = true> struct WgFft {
     static constexpr int E = 16;
     static constexpr int T = N / 16;
@@ -424,7 +416,7 @@ template <typename R, int N, bool RESIDENT = true> struct WgFft {
     // independent transforms of the workgroup to each other (round 5: eight s_barrier per fused pass of the small grids --
     // the reference's own 512^2 / 1024^2 cases -- gone; LDS operations of one wave execute in issue order)
     static __device__ __forceinline__ void xbar() {
-        if constexpr (T <= 64 && HGS_WAVE_LOCAL_BARRIER) {
+        if constexpr (T <= 64) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
         } else {
@@ -624,7 +616,7 @@ __device__ __forceinline__ void wave_lds_order() {
 // A[(q p_hi) & 255] * B[q p_lo] (one complex product, 1.5 ulp).  7 KB per workgroup; filled by ltw_fill at kernel start.
 // What it buys is not the fetch itself (the table is L2-resident) but the in-order vmcnt queue: with twiddle loads inside
 // the transform, anything requested AHEAD of it -- the column's weights and targets -- is waited for at the first twiddle
-// (round 5, HGS_F64_WT_EARLY: slower), so they were requested after it and cost a full memory round trip per column
+// (round 5, slower: NOTEBOOK.md "Retired build switches", weights / targets requested early), so they were requested after it and cost a full memory round trip per column
 // (tools/microbench/trace8k f64main: 11.6 k of 45 k cycles).
 constexpr int LTW_A = 256, LTW_B = 192, LTW_N = LTW_A + LTW_B;
 template <typename R, bool RESIDENT = true, int TS = 1, bool RAWBAR = false, int ES = 1, bool LTW = false> struct WgFftL {
@@ -663,11 +655,6 @@ template <typename R, bool RESIDENT = true, int TS = 1, bool RAWBAR = false, int
     }
     __device__ __forceinline__ void init(const Cx<R>* __restrict__ table, int p) {
         table_ = table;
-        if (HGS_PRIO == 1) {
-            unsigned hw;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 4)" : "=s"(hw));     // wave slot within the SIMD
-            if (hw & 1u) __builtin_amdgcn_s_setprio(1);
-        }
         if constexpr (RESIDENT) {
             static_for<0, 6>([&](auto i_) {
                 constexpr int i = i_;
@@ -680,14 +667,12 @@ template <typename R, bool RESIDENT = true, int TS = 1, bool RAWBAR = false, int
 
     template <int DIR, int s> __device__ __forceinline__ void butterfly_pre(Cx<R> (&v)[16], int p) {
         if (HGS_ABL_BFLY) return;
-        if (HGS_PRIO == 2) __builtin_amdgcn_s_setprio(2);
         static_for<1, 4>([&](auto r2_) {
             constexpr int r2 = r2_;
             cmul4<DIR>(v[4 * r2], v[4 * r2 + 1], v[4 * r2 + 2], v[4 * r2 + 3], this->template twv<s, r2 - 1>(p));
         });
         Dft<16, DIR, R>::template run_tw<true>(v, this->template twv<s, 3>(p), this->template twv<s, 4>(p),
                                                this->template twv<s, 5>(p));
-        if (HGS_PRIO == 2) __builtin_amdgcn_s_setprio(0);
     }
     template <int DIR, int s> __device__ __forceinline__ void butterfly_post(Cx<R> (&v)[16], int p) {
         if (HGS_ABL_BFLY) return;
@@ -789,16 +774,12 @@ template <typename R, bool RESIDENT = true, int TS = 1, bool RAWBAR = false, int
 // partner x[n + 4096] is zero, the radix-2 step is a copy and a twiddle) become 2 NZ leading slots of the 4096-point
 // transforms; likewise NOUT on the way back.
 template <typename R, bool RESIDENT = true, bool RAWBAR = false, bool LTW = false> struct WgFftL8k {
-#ifndef HGS_8K_INTERLEAVE
-#define HGS_8K_INTERLEAVE 1
-#endif
     // images interleaved element by element (element e of image h at 2 e + h): consecutive lanes (p, 0), (p, 1) touch
     // consecutive elements, so a 16-lane group of a ds_write_b64 (served on 32 banks) covers 16 different bank pairs.
-    // (Images 16 elements apart instead, HGS_8K_INTERLEAVE = 0: both halves of 8 lanes on the same 8 pairs, every cross-lane
-    //  write 2-way conflicted, SQ_LDS_BANK_CONFLICT 40 % of the array cycles.)
-    static constexpr bool IL = HGS_8K_INTERLEAVE != 0;
-    static constexpr int N = 8192, T = 512, IMG = IL ? 1 : 16 * 272 + 16, X1 = IL ? 513 : IMG + 1, WREG = IL ? 1088 : 544;
-    using Core = WgFftL<R, RESIDENT, 2, RAWBAR, IL ? 2 : 1, LTW>;
+    // (Images 16 elements apart instead: both halves of 8 lanes on the same 8 pairs, every cross-lane write 2-way conflicted,
+    //  SQ_LDS_BANK_CONFLICT 40 % of the array cycles.)
+    static constexpr int N = 8192, T = 512, IMG = 1, X1 = 513, WREG = 1088;
+    using Core = WgFftL<R, RESIDENT, 2, RAWBAR, 2, LTW>;
     Core core;
     static __device__ __forceinline__ void ltw_fill(const Cx<R>* __restrict__ table, Cx<R>* ltw, int tid, int nthreads) { Core::ltw_fill(table, ltw, tid, nthreads); }
     __device__ __forceinline__ void set_ltw(const Cx<R>* ltw) { core.set_ltw(ltw); }
@@ -890,30 +871,20 @@ template <typename R, bool RESIDENT = true, bool RAWBAR = false, bool LTW = fals
 
 // Which workgroup transform a kernel uses for length N, and where lane j's elements sit on the space side
 // (frequency side: always j + m * N/16).
-#ifndef HGS_LOCAL_FFT
-#define HGS_LOCAL_FFT 1
-#endif
 template <typename R, int N, bool RESIDENT, bool RAWBAR = false, bool LTW = false> struct FftSel {
     using type = WgFft<R, N, RESIDENT>;
     static constexpr bool local = false;
     static __host__ __device__ __forceinline__ int space_lane(int j) { return j; }
 };
-#if HGS_LOCAL_FFT
 template <typename R, bool RESIDENT, bool RAWBAR, bool LTW> struct FftSel<R, 4096, RESIDENT, RAWBAR, LTW> {
     using type = WgFftL<R, RESIDENT, 1, RAWBAR, 1, LTW>;
     static constexpr bool local = true;
     static __host__ __device__ __forceinline__ int space_lane(int j) { return WgFftL<R, RESIDENT>::space_lane(j); }
 };
-#ifndef HGS_LOCAL_FFT8K
-#define HGS_LOCAL_FFT8K 1
-#endif
-#if HGS_LOCAL_FFT8K
 template <typename R, bool RESIDENT, bool RAWBAR, bool LTW> struct FftSel<R, 8192, RESIDENT, RAWBAR, LTW> {
     using type = WgFftL8k<R, RESIDENT, RAWBAR, LTW>;
     static constexpr bool local = true;
     static __host__ __device__ __forceinline__ int space_lane(int j) { return WgFftL8k<R, RESIDENT>::space_lane(j); }
 };
-#endif
-#endif
 
 }  // namespace hgs

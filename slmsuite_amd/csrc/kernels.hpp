@@ -17,102 +17,57 @@
 #pragma once
 #include "fft_core.hpp"
 
-// minimum waves per SIMD the transform kernels are register-allocated for (tunable at build time)
+// ---- build switches ------------------------------------------------------------------------------------
+// Everything a build can set from the command line.  None of them is a decision left open: they are numeric tunables and
+// measurement instruments of the committed tools.  (The transform's own instruments -- HGS_TRACE, HGS_TRACE_OFF,
+// HGS_TRACE_SKIP, HGS_ABL_XCHG, HGS_ABL_BFLY, HGS_ABL_TRANS -- sit at the top of fft_core.hpp, which some microbenchmarks
+// include on its own.  Switches that were settled and removed: NOTEBOOK.md "Retired build switches".)
+// minimum waves per SIMD the transform kernels are register-allocated for
 #ifndef HGS_COL_OCC_8192
-#define HGS_COL_OCC_8192 4
+#define HGS_COL_OCC_8192 4        // set by: A/B builds (tools/build_variant.sh)
 #endif
 #ifndef HGS_ROW_OCC_8192
-#define HGS_ROW_OCC_8192 4
+#define HGS_ROW_OCC_8192 4        // set by: A/B builds (tools/build_variant.sh)
 #endif
 #ifndef HGS_ROW_OCC
-#define HGS_ROW_OCC 3
+#define HGS_ROW_OCC 3             // set by: A/B builds (tools/build_variant.sh; NOTEBOOK.md has -DHGS_ROW_OCC=4)
 #endif
 #ifndef HGS_COL_OCC
-#define HGS_COL_OCC 3
-#endif
-#ifndef HGS_ROW_TW_RESIDENT
-#define HGS_ROW_TW_RESIDENT true
-#endif
-#ifndef HGS_COL_BUF
-#define HGS_COL_BUF 1        // fused column kernel: G / H columns through a buffer resource (see Buf)
-#endif
-#ifndef HGS_ROW_BUF
-#define HGS_ROW_BUF 1        // row kernel: raw buffer accesses, straight-line (rows whose lane group is a whole number of waves)
-#endif
-#ifndef HGS_ROW_PHASOR
-#define HGS_ROW_PHASOR 1     // MODE 2 row kernel: nf/|nf| instead of atan2 + sincos
-#endif
-#ifndef HGS_ROW_PREF_NOMASK
-#define HGS_ROW_PREF_NOMASK 0  // 1: ... or keeps its flat stores but drops the mask test (one block of sixteen stores): 26.0 -> 27.9 us -- slower too:
-#endif                         //    the per-store blocks keep the stores spread between the last butterflies instead of bunched behind them
-#ifndef HGS_ROW_PREF_BUFST
-#define HGS_ROW_PREF_BUFST 0   // 1: the prefetching row walk stores G through a buffer resource, straight-line (no mask test, no 64-bit address
-#endif                         //    per store): row launch 26.0 -> 28.1 us, headline 15.17 k -> 14.65 k it/s -- slower (round 6)
-#ifndef HGS_LIST_SLOAD
-#define HGS_LIST_SLOAD 1
-#endif
-#ifndef HGS_ROW_AMP_PREFETCH
-#define HGS_ROW_AMP_PREFETCH 1
-#endif
-#ifndef HGS_SPARSE_SKIP
-#define HGS_SPARSE_SKIP 1
+#define HGS_COL_OCC 3             // set by: A/B builds (tools/build_variant.sh)
 #endif
 #ifndef HGS_FUSED_OCC
-#define HGS_FUSED_OCC 2
+#define HGS_FUSED_OCC 2           // set by: A/B builds (tools/build_variant.sh)
 #endif
-// Ablation hooks for tools/microbench/ablate.hip (all 0 in the product build): compile the weight/target
-// loads (WT) or the GH tile loads and stores (GH) out of col_tile_kernel to see what they cost.
-// Round-5 experiments on the 8192-row column kernels, all measured and NOT adopted (NOTEBOOK.md; A/B builds through
-// tools/microbench/build_trace8k.sh): the s_memtime trace of a build that drains vmcnt at every phase boundary suggested
-// memory waits that the product build does not have.
-#ifndef HGS_ROW_AMP_LATE
-#define HGS_ROW_AMP_LATE 0      // row_kernel PREF: 1 = the amplitude requests behind the pick-up of the staged row (measured, below)
+// pixels of a lane whose rule evaluation the scheduler may interleave
+#ifndef HGS_CONS_GROUP
+#define HGS_CONS_GROUP 16         // fp32 (fp64 in col_tile_kernel: 4); set by: A/B builds (tools/build_variant.sh)
 #endif
-#ifndef HGS_TILE_TOUCH
-#define HGS_TILE_TOUCH 1        // col_tile_kernel, 8192 rows: the wait for a column's weights / targets sits at the END of the previous column
-#endif                          // (an empty asm that names their registers), not at its head -- see the kernel
-#ifndef HGS_TILE_STAGE_WAIT
-#define HGS_TILE_STAGE_WAIT 1   // 0: no vmcnt(0) ahead of reading the staged tile (the loads have landed by then): 213.9 vs 214.5 us, noise
+#ifndef HGS_CONS_GROUP_F64
+#define HGS_CONS_GROUP_F64 1      // float64: one pixel at a time (four interleaved double atan2 / sincos / log2 chains cost 100+ registers);
+#endif                            // set by: A/B builds (tools/build_variant.sh)
+#ifndef HGS_TILE2_CONS_GROUP
+#define HGS_TILE2_CONS_GROUP 4    // col_tile2_kernel (168 registers: fewer than col_tile_kernel's 16); set by: A/B builds (NOTEBOOK.md, ab_tile2_cons_group.log)
 #endif
-#ifndef HGS_F64_WT_PREFETCH
-#define HGS_F64_WT_PREFETCH 0   // 1: float64 8192-point fused kernel, one word of each weight / target line requested ahead of the forward
-#endif                          //    transform (L2 prefetch): 737 vs 713 us -- slower
-#ifndef HGS_PF_AHEAD
-#define HGS_PF_AHEAD 1          // per-column kernel, fp32, fixed farfield phase: the stored phase fetched a column ahead with the weights
-#endif
-#ifndef HGS_F64_WT_EARLY
-#define HGS_F64_WT_EARLY 0      // float64 8192-point fused kernel, shifted form: weights / targets requested ahead of the (pruned) forward transform
-#endif
-#ifndef HGS_SPLIT_L2_PREFETCH
-#define HGS_SPLIT_L2_PREFETCH 0 // 1: single-pass MRAF tile kernel, the next tile's rows requested ahead of the first transform: 332.6 vs 330.4 us
-#endif
-#ifndef HGS_F64_POW_LEAN
-#define HGS_F64_POW_LEAN 1      // float64 rule kernels: pow_lean / Newton rsqrt instead of ocml's log2 + exp2 / sqrt + division (round 6)
-#endif
-#ifndef HGS_F64_PARK_AHEAD
-#define HGS_F64_PARK_AHEAD 0    // 1: float64 fused kernel, the parked value of pixel m + 1 requested before pixel m is evaluated: 620 vs 599 us (slower; round 6)
-#endif
+// ablation hooks (all 0 in the product build): compile the weight / target loads (WT) or the GH tile loads and stores (GH) out of
+// col_tile_kernel to see what they cost
 #ifndef HGS_ABL_WT
-#define HGS_ABL_WT 0
+#define HGS_ABL_WT 0              // set by: tools/microbench/build_ablate.sh
 #endif
 #ifndef HGS_ABL_GH
-#define HGS_ABL_GH 0
+#define HGS_ABL_GH 0              // set by: tools/microbench/build_ablate.sh
+#endif
+#ifndef HGS_PRESUM_ABL
+#define HGS_PRESUM_ABL 0          // 1 = the pre-pass loads no weights, 2 = neither weights nor targets; set by: tools/build_variant.sh builds
+#endif
+#ifndef HGS_TRACE_CONS
+#define HGS_TRACE_CONS 0          // one event per pixel of the float64 constraint; set by: traced builds of tools/microbench/trace8k.hip
 #endif
 
 namespace hgs {
 
-#ifndef HGS_F64_LTW
-#define HGS_F64_LTW 1
-#endif
-#ifndef HGS_F64_WT_BUF
-#define HGS_F64_WT_BUF 1
-#endif
-#ifndef HGS_F64_LTW_ROW
-#define HGS_F64_LTW_ROW 0       // 1: the float64 row kernel's stage twiddles from the LDS tables too: 106.3 vs 106.4 us at cfg 5, nothing (round 6)
-#endif
-// float64 transform kernels at 4096 / 8192 points (col_fused_kernel, row_kernel): stage twiddles from the two LDS tables of
+// float64 transform kernels at 4096 / 8192 points (col_fused_kernel): stage twiddles from the two LDS tables of
 // WgFftL LTW, and the dynamic LDS they add behind the kernel's other LDS
-template <typename R, int N> constexpr bool fused_ltw() { return HGS_F64_LTW && sizeof(R) == 8 && (N == 4096 || N == 8192); }
+template <typename R, int N> constexpr bool fused_ltw() { return sizeof(R) == 8 && (N == 4096 || N == 8192); }
 template <typename R, int N> constexpr size_t fused_ltw_bytes() { return fused_ltw<R, N>() ? (size_t)LTW_N * sizeof(Cx<R>) : 0; }
 
 struct Geo {
@@ -125,38 +80,11 @@ struct Geo {
 // so the 16 values a lane needs are 64 contiguous bytes (4 x 16-byte loads instead of 16 scalar
 // ones, 4 KiB contiguous per wave).  Elementwise kernels are oblivious to the permutation;
 // hgs_set_array / hgs_get_array and the spot kernels apply it.
-// Tile-resident column kernel: pick the column of the pass out of the tile registers with a register-relative move
-// (the pass index is uniform: s_set_gpr_idx + v_mov, 24 instructions per pass) instead of 84 v_cndmask
-#ifndef HGS_ROW_LD16
-#define HGS_ROW_LD16 1      // ... and load H in 16-byte pieces
-#endif
-#ifndef HGS_ROW_ST16
-#define HGS_ROW_ST16 1      // dense fp32 row launches store G in 16-byte pieces (lane pairs swap one value per slot pair)
-#endif
-#ifndef HGS_TILE_MOVREL
-#define HGS_TILE_MOVREL 1
-#endif
-#ifndef HGS_CONS_GROUP
-#define HGS_CONS_GROUP 16    // pixels of a lane whose rule evaluation the scheduler may interleave (fp32; fp64: 4)
-#endif
-#ifndef HGS_TRACE_CONS
-#define HGS_TRACE_CONS 0      // traced builds (tools/microbench/trace8k): one event per pixel of the float64 constraint
-#endif
-#ifndef HGS_F64_EAGER
-#define HGS_F64_EAGER 0       // 1: float64 rule and phasor evaluated for every lane and selected, as in float32, so that HGS_CONS_GROUP_F64
-                              //    pixels form one scheduling region (also with -amdgpu-sched-strategy=max-ilp): 543 vs 543 us, nothing (round 6)
-#endif
-#ifndef HGS_CONS_GROUP_F64
-#define HGS_CONS_GROUP_F64 1  // float64: one pixel at a time (four interleaved double atan2 / sincos / log2 chains cost 100+ registers)
-#endif
-#ifndef HGS_LANE_MAJOR
-#define HGS_LANE_MAJOR 1
-#endif
 __host__ __device__ __forceinline__ int col_pos(int ky, int T) {
-    return (HGS_LANE_MAJOR && T > 0) ? (ky % T) * 16 + ky / T : ky;
+    return T > 0 ? (ky % T) * 16 + ky / T : ky;
 }
 template <int T> __device__ __forceinline__ unsigned lane_pos(int j, int m) {
-    return HGS_LANE_MAJOR ? (unsigned)(j * 16 + m) : (unsigned)(j + m * T);
+    return (unsigned)(j * 16 + m);
 }
 
 // method codes follow ALGORITHM_INDEX (_header.py:72)
@@ -241,10 +169,6 @@ template <> struct Math<float> {
     static __device__ __forceinline__ float exp(float x) { return expf(x); }
     static __device__ __forceinline__ float log2(float x) { return log2f(x); }
     static __device__ __forceinline__ float exp2(float x) { return exp2f(x); }
-    // bare v_log_f32 / v_exp_f32 (1 ulp each, no denormal rescaling: 4 instead of 19 instructions for x^p); for
-    // arguments in the normal range only -- the weight rule's ratio (|F| c / T)^2 near 1
-    static __device__ __forceinline__ float log2_fast(float x) { return __builtin_amdgcn_logf(x); }
-    static __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
     static __device__ __forceinline__ float tanh(float x) { return tanhf(x); }
     static __device__ __forceinline__ float abs(float x) { return fabsf(x); }
 };
@@ -259,8 +183,6 @@ template <> struct Math<double> {
     static __device__ __forceinline__ double exp(double x) { return ::exp(x); }
     static __device__ __forceinline__ double log2(double x) { return ::log2(x); }
     static __device__ __forceinline__ double exp2(double x) { return ::exp2(x); }
-    static __device__ __forceinline__ double log2_fast(double x) { return ::log2(x); }
-    static __device__ __forceinline__ double exp2_fast(double x) { return ::exp2(x); }
     static __device__ __forceinline__ double tanh(double x) { return ::tanh(x); }
     static __device__ __forceinline__ double abs(double x) { return ::fabs(x); }
 };
@@ -444,17 +366,12 @@ __device__ __forceinline__ double pow_lean(double x, double c) {
 // (|F| c / T)^-p for the Leonardo / Kim rule of the fused kernels, from |F|^2: the ratio is formed FIRST (log2 of the
 // three factors separately cancels ~20 against ~20 and leaves 1e-6 relative noise per update).
 template <typename R> __device__ __forceinline__ R leonardo_factor(R p2, R t, R inv_fnorm, R p_exp) {
-    using M = Math<R>;
     const R q = inv_fnorm * Math<R>::rcp(t);       // 1-ulp reciprocal: the ratio is squared and raised to p/2 < 1/2
     const R r2 = p2 * q * q;                       // (|F| c / T)^2
     if (!(r2 < (R)INFINITY)) return (R)1;          // overflow of the ratio (:1840) and NaN targets (:1843) -> 1
     // r2 = 0 -> inf: callers map it to 1 (:1867)
     if constexpr (sizeof(R) == 4) return pow_split(r2, -0.5f * p_exp);
-#if HGS_F64_POW_LEAN
     else return pow_lean(r2, (R)-0.5 * p_exp);
-#else
-    else return M::exp2_fast((R)-0.5 * p_exp * M::log2_fast(r2));
-#endif
 }
 
 // ---- the WGS weight rule for one element (rows 9-10; _hologram.py:1830-1873) -------------------------
@@ -532,7 +449,6 @@ __device__ __forceinline__ float rsqrt_full(float x) {
 }
 // float64: the hardware estimate and two Newton steps (x > 0; a sqrt and a division in double are some fifty instructions)
 __device__ __forceinline__ double rsqrt_full(double x) {
-#if HGS_F64_POW_LEAN
     const bool tiny = x < 0x1p-900;
     const double xs = tiny ? x * 0x1p+200 : x;
     double y = __builtin_amdgcn_rsq(xs);
@@ -540,9 +456,6 @@ __device__ __forceinline__ double rsqrt_full(double x) {
     y = __builtin_fma(y, __builtin_fma(-h * y, y, 0.5), y);
     y = __builtin_fma(y, __builtin_fma(-h * y, y, 0.5), y);
     return tiny ? y * 0x1p+100 : y;
-#else
-    return 1.0 / ::sqrt(x);
-#endif
 }
 
 // =====================================================================================================
@@ -655,19 +568,10 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
     // (fp64: 64 data registers per lane already; the stage twiddles are fetched per use instead of kept)
     // (fp32 instances that ran out of registers with them -- every phase-extracting launch, i.e. one per engine call, and the
     //  unshifted 8192-wide form -- fetch them per use as well: 8 .. 48 spilled VGPRs -> 0, tools/resusage.sh)
-    constexpr bool TW_RES = sizeof(R) == 8 ? false : (MODE == 1 || MODE == 3 || (N >= 8192 && NS == 16)) ? false : HGS_ROW_TW_RESIDENT;
-    // float64 rows of 4096 / 8192 columns: the per-use stage twiddles from LDS tables instead of global loads inside the
-    // transform's dependent chain (round 6; the tables sit behind the transform image)
-    constexpr bool LTW = fused_ltw<R, N>() && !TW_RES && HGS_F64_LTW_ROW;
-    using Sel = FftSel<R, N, TW_RES, PREF, LTW>;
+    constexpr bool TW_RES = sizeof(R) == 4 && !(MODE == 1 || MODE == 3 || (N >= 8192 && NS == 16));
+    using Sel = FftSel<R, N, TW_RES, PREF>;
     typename Sel::type fft;
     fft.init(a.tw, j);
-    if constexpr (LTW) {
-        Cx<R>* ltab = reinterpret_cast<Cx<R>*>(smem) + FPW * lds_elems<N>();
-        Sel::type::ltw_fill(a.tw, ltab, tid, (int)blockDim.x);
-        fft.set_ltw(ltab);
-        __syncthreads();
-    }
 
     // lane j owns elements j + m*T of the frequency side (GH columns) and js + m*T of the space side (SLM columns)
     const int js = Sel::space_lane(j);
@@ -756,7 +660,7 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
         // (measured: 2048^2 22.5 -> 21.5 us, 1024^2 10.8 -> 10.2 us; 4096 / 8192-wide rows lose 1 us with it -- their
         //  one-row workgroups gain nothing from the shorter code and pay for the 8 more eager phasors -- and keep the
         //  branching form)
-        if constexpr (HGS_ROW_BUF && T % 64 == 0 && T <= 128) {
+        if constexpr (T % 64 == 0 && T <= 128) {
             // ---- straight-line form: raw buffer accesses (see Buf), no per-element branch ----
             // resources of this row (wave-uniform); a row past Sh gets empty ones: loads give 0, stores vanish
             constexpr unsigned CB = sizeof(Cx<R>), RB = sizeof(R);
@@ -844,16 +748,15 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
         // one).  Fetched where it is used -- inside the per-slot exec-masked block of the phasor, `s_waitcnt vmcnt(0)` right
         // behind each load -- it was NS dependent memory round trips per row: cfg 2 with a Gaussian amplitude 73.0 against
         // 65.5 us per iteration with the scalar one (tools/amp_array_probe.py, round 6).
-        constexpr bool AMPF = HGS_ROW_AMP_PREFETCH && MODE >= 2 && T % 64 == 0 && !(N >= 8192 && NS == 16);
+        constexpr bool AMPF = MODE >= 2 && T % 64 == 0 && !(N >= 8192 && NS == 16);
         R amr[AMPF ? NS : 1];
         auto issue_amp = [&]() {
             const Buf bam(am, (am != nullptr && valid) ? (unsigned)g.Sw * (unsigned)sizeof(R) : 0u);
             static_for<0, NS>([&](auto m_) { constexpr int m = m_; amr[m] = bam.template ld<R>((unsigned)(c_lane + m * T) * (unsigned)sizeof(R), 0u); });
         };
-        // (PREF: behind the pick-up of the staged row -- ahead of it, the `s_waitcnt vmcnt(0)` that waits for the staged pieces
-        //  waited for these requests as well, a round trip at the head of every row)
-        constexpr bool AMP_LATE = AMPF && PREF && MODE != 0 && HGS_ROW_AMP_LATE;
-        if constexpr (AMPF && !AMP_LATE) issue_amp();
+        // (PREF: the `s_waitcnt vmcnt(0)` that waits for the staged pieces waits for these requests as well; requesting them
+        //  behind the pick-up of the staged row instead was tried: NOTEBOOK.md "Retired build switches")
+        if constexpr (AMPF) issue_amp();
         if constexpr (MODE != 0) {
             // ---- load H row, centred inverse transform along x ----
             if constexpr (PREF) {
@@ -872,14 +775,13 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 HGS_T(fft.tr_n, 32);
                 if (rbase + row_stride < g.Sh) prefetch_row(rbase + row_stride);
-                if constexpr (AMP_LATE) issue_amp();
                 HGS_T(fft.tr_n, 33);
             } else {
             // dense fp32 launches: the H row in 16-byte pieces, the lane pair swapping one value per slot pair (see the G stores)
             bool wide = false;
-            if constexpr (sizeof(R) == 4 && HGS_ROW_LD16 && T % 64 == 0) wide = a.load_mask == nullptr && valid;
+            if constexpr (sizeof(R) == 4 && T % 64 == 0) wide = a.load_mask == nullptr && valid;
             if (wide) {
-                if constexpr (sizeof(R) == 4 && HGS_ROW_LD16 && T % 64 == 0) {
+                if constexpr (sizeof(R) == 4 && T % 64 == 0) {
                     const bool odd = (j & 1) != 0;
                     const Cx<R>* pbase = ghr + (gh_lane - (odd ? 1u : 0u)) + (odd ? (size_t)gh_step : (size_t)0);
                     float4 q[8];
@@ -976,19 +878,11 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                         if (kn != nullptr) p -= kn[c];
                         ph[c] = p;
                     }
-                    if constexpr (MODE >= 2 && HGS_ROW_PHASOR) {        // ... and G exactly as MODE 2 builds it
+                    if constexpr (MODE >= 2) {        // ... and G exactly as MODE 2 builds it
                         // nearfield of the inverse = sgn*scale*v, input of the forward = sgn*amp*phasor
                         const R p2 = v[m].x * v[m].x + v[m].y * v[m].y;
                         const Cx<R> on = v[m] * (amv * rsqrt_full(p2));      // (eager + select: no inner branches)
                         nf = mk<R>((p2 > (R)0) ? on.x : amv * sgs, (p2 > (R)0) ? on.y : (R)0);
-                    } else if constexpr (MODE >= 2) {
-                        // the reference's own arithmetic: phase rounded to working precision, then exp(i phase)
-                        const R scs = sgs * a.scale;
-                        R p = M::atan2(v[m].y * scs, v[m].x * scs);
-                        if (kn != nullptr) { p -= kn[c]; p += kn[c]; }
-                        R s, co;
-                        M::sincos(p, &s, &co);
-                        nf = mk<R>(amv * sgs * co, amv * sgs * s);
                     } else {
                         R p = ph[c];
                         if (kn != nullptr) p += kn[c];
@@ -1014,21 +908,7 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                 // slot m + 1 -- eight store instructions instead of sixteen, the same bytes at the same addresses.
                 // (measured: a batch of eight, one-row workgroups: row launch 89.8 -> 86.9 us; the prefetching walk of a single
                 //  hologram LOSES 1.2 us to the swaps on its chain and keeps the 8-byte stores; 8192-wide rows: level)
-                if constexpr (PREF && HGS_ROW_PREF_BUFST) {
-                    // the prefetching walk (dense launches only: no store mask): sixteen straight-line stores through a buffer
-                    // resource -- the lane part of the address one VGPR offset, the register part an SGPR offset.  As plain stores
-                    // each sat in its own exec-masked block (the mask test) with a 64-bit address computed in front of it
-                    // (launch_row_f32.s: s_and_saveexec / s_cbranch / s_mul / s_add / v_lshl_add_u64 per store)
-                    const Buf bg(gh, (unsigned)((size_t)g.Sh * g.Pw * sizeof(Cx<R>)));
-                    const unsigned vo = (gh_lane + (unsigned)rr * 4u) * (unsigned)sizeof(Cx<R>);
-                    static_for<0, 16>([&](auto m_) {
-                        constexpr int m = m_;
-                        Cx<R> e;
-                        if constexpr (NS < 16) e = cmul(v[m], omsc); else e = v[m] * sc;
-                        bg.template st<Cx<R>>(e, vo, (unsigned)m * gh_step * (unsigned)sizeof(Cx<R>));
-                    });
-                } else
-                if constexpr (sizeof(R) == 4 && HGS_ROW_ST16 && T % 64 == 0 && !PREF) {
+                if constexpr (sizeof(R) == 4 && T % 64 == 0 && !PREF) {
                     if (a.store_mask == nullptr) {
                         const bool odd = (j & 1) != 0;
                         Cx<R>* pbase = ghr + (gh_lane - (odd ? 1u : 0u)) + (odd ? (size_t)gh_step : (size_t)0);
@@ -1056,8 +936,7 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                 } else
                 static_for<0, 16>([&](auto m_) {
                     constexpr int m = m_;
-                    // (the prefetching walk is launched dense-only: no mask test, so that its sixteen stores are one block)
-                    if ((PREF && HGS_ROW_PREF_NOMASK) || ((smask >> m) & 1u)) {
+                    if ((smask >> m) & 1u) {
                         if constexpr (NS < 16) (ghr + (size_t)m * gh_step)[gh_lane] = cmul(v[m], omsc);
                         else (ghr + (size_t)m * gh_step)[gh_lane] = v[m] * sc;
                     }
@@ -1198,7 +1077,7 @@ __global__ __launch_bounds__(ColCfg<N>::WG, (sizeof(R) == 8 ? 2 : N >= 8192 ? HG
             const size_t cb = (size_t)b * P + (size_t)kx * g.Ph;   // column base in the P arrays
             Cx<R> v[16];
             // (rows outside the SLM through the range check of a buffer resource where the column is wave-uniform)
-            constexpr bool GBUF = HGS_COL_BUF && T % 64 == 0;
+            constexpr bool GBUF = T % 64 == 0;
             constexpr unsigned CB = sizeof(Cx<R>);
             const Buf bg(gh + c4, vcol ? (unsigned)(g.Sh * 4 - c4) * CB : 0u);
             const unsigned g_voff = (unsigned)r_lane * 4u * CB, g_vstep = (unsigned)T * 4u * CB;
@@ -1395,7 +1274,7 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
     // PHASE 2 (fixed farfield phase, the steady state of WGS-Kim), fp32: the stored phase of a column arrives with its weights
     // and targets, a column ahead (16 more registers, 189 -> ~205 of 256), instead of being fetched pixel by pixel inside the
     // constraint -- on a column list (engine default) that fetch sat on the ~12 us chain of the launch (round 5)
-    constexpr bool PF_AHEAD = PHASE == 2 && !LEAN && HGS_PF_AHEAD && HGS_LANE_MAJOR;
+    constexpr bool PF_AHEAD = PHASE == 2 && !LEAN;
     float4 pfq0 = make_float4(0, 0, 0, 0), pfq1 = pfq0, pfq2 = pfq0, pfq3 = pfq0;      // (four 16-byte registers, not an array: R[16] left 12 bytes on the stack)
 
     // (list launches: the entry of sweep q is asked for three times per column -- at the top of the loop, by the weight /
@@ -1408,7 +1287,7 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
     auto col_of = [&](int q, int& ct, int& c4) {
         if (listed) {
             int col;
-            if constexpr (T % 64 == 0 && HGS_LIST_SLOAD) {
+            if constexpr (T % 64 == 0) {
                 if (q != col_cache_q) { col_cache = uniform_load_i32(clist + min(grp_of(q) * CPAR + cpar, n_act - 1)); col_cache_q = q; }
                 col = col_cache;
             } else {
@@ -1439,8 +1318,9 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
         // inside uniform branches the compiler does not know at the join how many are in flight and waits for the OLDER loads
         // of the column's G rows with vmcnt(0..3) -- i.e. for the weights and targets just requested as well: the in-order
         // queue then costs a full memory round trip per column exactly where the request was meant to run ahead of the
-        // transform (tools/microbench/trace8k f64main: 11 k of 45 k cycles; what HGS_F64_WT_EARLY ran into in round 5).
-        if constexpr (LEAN && HGS_LANE_MAJOR && HGS_COL_BUF && T % 64 == 0 && HGS_F64_WT_BUF) {
+        // transform (tools/microbench/trace8k f64main: 11 k of 45 k cycles; what the early request of round 5 ran into: NOTEBOOK.md
+        // "Retired build switches").
+        if constexpr (LEAN && T % 64 == 0) {
             constexpr unsigned RB = sizeof(R), PER = 16 / RB;           // values per 16-byte load
             const unsigned bytes = col_valid(q) ? (unsigned)g.Ph * RB : 0u;
             const Buf bw(wc, bytes), bt(tc, need_t ? bytes : 0u);
@@ -1474,7 +1354,7 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
     };
     // rows outside the SLM (and whole columns past the end of a list) through the range check of a buffer resource
     // where the column of a lane is wave-uniform: 16 straight-line loads / stores instead of 16 branches
-    constexpr bool GBUF = HGS_COL_BUF && T % 64 == 0;
+    constexpr bool GBUF = T % 64 == 0;
     constexpr unsigned CB = sizeof(Cx<R>);
     auto g_buf = [&](int q, int ct, int c4) {
         const Cx<R>* gh = a.gh + (size_t)b * g.Sh * g.Pw + (size_t)ct * g.Sh * 4 + c4;
@@ -1519,20 +1399,12 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
         static_for<0, NRS>([&](auto m_) { constexpr int m = m_; v[m] = v[m] * sgs; });
         // fp64: this column's weights / targets land under its forward transform (8192: after it -- the 64 registers
         // would not fit next to the transform's own)
-        if constexpr (LEAN && (N < 8192 || (SHIFTED && (HGS_F64_WT_EARLY || LTW)))) issue_wt(q);
+        if constexpr (LEAN && (N < 8192 || (SHIFTED && LTW))) issue_wt(q);
         // 8192 points: the 64 registers of this column's weights / targets do not fit next to the forward transform, so they
-        // are requested after it.  (Experiment, off: one word of each of the lane's two 128-byte lines requested BEFORE the
-        // transform, so that the real loads are L2 hits -- the launch got 3 % slower, HGS_F64_WT_PREFETCH.)
-        int pf_w = 0, pf_t = 0;
-        if constexpr (LEAN && N >= 8192 && HGS_F64_WT_PREFETCH) {
-            if (vcol) {
-                pf_w = reinterpret_cast<const int*>(a.w + cb + lane_pos<T>(j, 0))[0];
-                if (do_upd || STATS || x_mraf) pf_t = reinterpret_cast<const int*>(a.t + cb + lane_pos<T>(j, 0))[0];
-            }
-        }
+        // are requested after it.  (One word of each of the lane's two 128-byte lines requested BEFORE the transform, so that the
+        // real loads are L2 hits, made the launch 3 % slower: NOTEBOOK.md "Retired build switches".)
         if constexpr (SHIFTED) fft.template fwd_lead<NRS>(v, lds, j);       // slots NRS.. are zero (rows outside the SLM)
         else fft.fwd(v, lds, j);
-        if constexpr (LEAN && N >= 8192 && HGS_F64_WT_PREFETCH) asm volatile("" :: "v"(pf_w), "v"(pf_t));
         HGS_T(fft.tr_n, 3);
         // fp64: the 16 transformed values of a lane (64 VGPRs) wait in the idle LDS image while the constraint runs --
         // lane-private slots [m * T + j], conflict-free, no barrier -- so that the rule (inlined double log2 / exp2,
@@ -1541,7 +1413,7 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
         Cx<R>* park = lds + j;
         if constexpr (LEAN) {
             static_for<0, 16>([&](auto m_) { constexpr int m = m_; park[m * T] = v[m]; });
-            if constexpr (N >= 8192 && !(SHIFTED && (HGS_F64_WT_EARLY || LTW))) issue_wt(q);
+            if constexpr (N >= 8192 && !(SHIFTED && LTW)) issue_wt(q);
         }
 #if HGS_TRACE
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1552,21 +1424,14 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
         R* wc = a.w + cb;
         R* pfc = (PHASE != 0) ? a.pff + cb : nullptr;
         bool w_changed = false;
-        // fp64: the parked value of pixel m + 1 is requested before pixel m is evaluated (one pixel at a time -- a scheduling
-        // barrier per pixel -- otherwise meant one exposed LDS round trip per pixel, sixteen per column)
-        Cx<R> vnext = mk<R>(0, 0);
-        if constexpr (LEAN && HGS_F64_PARK_AHEAD) vnext = park[0];
         auto cons = [&](auto m_) {
             constexpr int m = m_;
             const unsigned idx = lane_pos<T>(j, m);
             Cx<R> vm;
-            if constexpr (LEAN && HGS_F64_PARK_AHEAD) {
-                vm = vnext;
-                if constexpr (m + 1 < 16) vnext = park[(m + 1) * T];
-            } else if constexpr (LEAN) vm = park[m * T]; else vm = v[m];
+            if constexpr (LEAN) vm = park[m * T]; else vm = v[m];
             [&]() {
             // wave-uniform skip of pixels with zero weight and zero target (see col_tile_kernel)
-            if (PHASE != 1 && !(STATS && (a.do_stats & 2)) && HGS_SPARSE_SKIP &&
+            if (PHASE != 1 && !(STATS && (a.do_stats & 2)) &&
                 __builtin_amdgcn_ballot_w64(wr[m] != (R)0 || ((do_upd || STATS || x_mraf) && tr[m] != (R)0)) == 0) {
                 vm = mk<R>(0, 0);
                 if (x_nog && vcol) acc_w += (R)1;      // T == 0 -> fc = 1 (:1841)
@@ -1588,9 +1453,7 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
                     // evaluated for every lane and selected (a branch per pixel splits the pass into 16 blocks):
                     // T == 0 -> factor 1 (:1841); inf (:1840,:1867) and nan (:1843) -> 1
                     // (fp64: the rule is some hundred instructions of double log2 / exp2 -- worth the branch)
-                    // (float64 too since round 6: pow_lean is 45 operations, and without the per-lane branch the pixels of a group
-                    //  are one basic block whose dependent chains the scheduler can interleave, HGS_CONS_GROUP_F64)
-                    if (sizeof(R) == 4 || HGS_F64_EAGER || t != (R)0) {
+                    if (sizeof(R) == 4 || t != (R)0) {
                         R fc = leonardo_factor<R>(p2, t, cp.inv_fnorm, cp.p_exp);
                         fc = (t != (R)0 && fc < (R)INFINITY) ? fc : (R)1;
                         wv *= fc;
@@ -1623,7 +1486,7 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
                 }
                 else M::sincos_phase(pfc[idx], &si, &co);
             } else {
-                if (sizeof(R) == 4 || HGS_F64_EAGER || p2 > (R)0) {         // exp(i*atan2(F)) == F/|F|; atan2(0,0) = 0 (quirk A6)
+                if (sizeof(R) == 4 || p2 > (R)0) {         // exp(i*atan2(F)) == F/|F|; atan2(0,0) = 0 (quirk A6)
                     const R inv = rsqrt_full(p2);
                     co = (p2 > (R)0) ? F.x * inv : (R)1;
                     si = (p2 > (R)0) ? F.y * inv : (R)0;
@@ -1933,7 +1796,7 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
     //  an update 201.6 -> 201.2; the MRAF form WITH the update 212.9 -> 214.7 -- left as it was.  Builds that differ in nothing but the
     //  form of an unrelated loop move these kernels by +- 1.5 %, so only the first figure says much.  The rows of a workgroup's first
     //  tile as straight-line buffer loads on top of it: +6 VGPRs and 2 % slower everywhere, not kept.)
-    constexpr bool TOUCH = HGS_TILE_TOUCH && TPREF && !SPLIT && RULE != 5;
+    constexpr bool TOUCH = TPREF && !SPLIT && RULE != 5;
     constexpr bool TR_DEAD = RULE == 2 && !STATS && !EXTRAS;      // (the target is never read: its registers are constants)
     auto touch_wt = [&]() { touch_regs16<R, !TR_DEAD>(wr, tr); };
 #pragma unroll 1
@@ -1961,9 +1824,9 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
         if constexpr (TPREF) {
             // this wave's own pieces (no other wave reads them).  (They were issued a whole tile ago and every column since has
             // waited for weights / targets requested after them, so the wait is formally redundant -- and it also waits for
-            // the tile stores issued just before; without it the launch measured the same, HGS_TILE_STAGE_WAIT.)
+            // the tile stores issued just before; without it the launch measured the same: NOTEBOOK.md "Retired build switches".)
             // (TOUCH: the wait at the end of the previous column covered them -- they are older than that column's weight requests)
-            if (HGS_TILE_STAGE_WAIT && !TOUCH && staged) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (!TOUCH && staged) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         auto put_row = [&](auto m_, const float4& lo, const float4& hi) {
             constexpr int m = m_;
@@ -1997,21 +1860,8 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
                 stage_next(next_ct());
             }
         }
-        // SPLIT: the LDS the staging would use holds the parked noise part.  (Experiment, off: one word of each row piece of
-        // the workgroup's NEXT tile requested now, so that its rows are L2 hits -- no gain, HGS_SPLIT_L2_PREFETCH.)
-        int pf_next[NR];
-        if constexpr (SPLIT && TPREF && NR <= 4 && HGS_SPLIT_L2_PREFETCH) {     // (six slots: no registers to spare)
-#pragma unroll
-            for (int m = 0; m < NR; ++m) pf_next[m] = 0;
-            if (more(next_ct())) {
-                const Cx<R>* ghn = a.gh + (size_t)b * g.Sh * g.Pw + (size_t)next_ct() * g.Sh * 4;
-#pragma unroll
-                for (int m = 0; m < NR; ++m) {
-                    const int r = r_lane + m * T;
-                    if (r >= 0 && r < g.Sh) pf_next[m] = reinterpret_cast<const int*>(ghn + (unsigned)r * 4u)[0];
-                }
-            }
-        }
+        // SPLIT: the LDS the staging would use holds the parked noise part.  (One word of each row piece of the workgroup's
+        // NEXT tile requested now, so that its rows are L2 hits, gained nothing: NOTEBOOK.md "Retired build switches".)
         int tile_noise = 0;          // SPLIT: any column of this tile with a noise pixel (wave-uniform)
         // PRESUM / NOUPD over a column list: the scan bytes of the tile's four columns, one aligned word through the scalar cache,
         // once per tile (as a plain load inside the column loop it was a vector load with a drain behind it at the head of every column)
@@ -2034,16 +1884,7 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
 #pragma unroll
             for (int m = 0; m < 16; ++m) {
                 if (m < NR) {
-#if HGS_TILE_MOVREL
                     R xr = gtx[m < NR ? m : 0][c], xi = gty[m < NR ? m : 0][c];     // (uniform index: register-relative move)
-#else
-                    R xr = gtx[m < NR ? m : 0][0], xi = gty[m < NR ? m : 0][0];
-#pragma unroll
-                    for (int cc = 1; cc < 4; ++cc) {
-                        xr = (c == cc) ? gtx[m < NR ? m : 0][cc] : xr;
-                        xi = (c == cc) ? gty[m < NR ? m : 0][cc] : xi;
-                    }
-#endif
                     v[m] = mk<R>(xr * sgs, xi * sgs);
                 } else {
                     v[m] = mk<R>(0, 0);
@@ -2087,7 +1928,7 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
                 // weight at zero (T == 0 -> factor 1, :1841) and the constrained field is w * e^{i phi} = 0.
                 // Skip the arithmetic when that holds for the whole wave (not when phase_ff or amp_ff of
                 // every pixel must be produced).
-                if (PHASE != 1 && !(STATS && (a.do_stats & 2)) && HGS_SPARSE_SKIP &&
+                if (PHASE != 1 && !(STATS && (a.do_stats & 2)) &&
                     __builtin_amdgcn_ballot_w64(wr[m] != (R)0 || tr[m] != (R)0) == 0) {
                     v[m] = mk<R>(0, 0);
                     if constexpr (SPLIT) park[m * T + j] = mk<R>(0, 0);
@@ -2191,16 +2032,8 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
 #pragma unroll
             for (int m = 0; m < NR; ++m) {
                 const Cx<R> h = v[m] * (sgs * a.scale);
-#if HGS_TILE_MOVREL
                 gtx[m][c] = h.x;
                 gty[m][c] = h.y;
-#else
-#pragma unroll
-                for (int cc = 0; cc < 4; ++cc) {
-                    gtx[m][cc] = (c == cc) ? h.x : gtx[m][cc];
-                    gty[m][cc] = (c == cc) ? h.y : gty[m][cc];
-                }
-#endif
             }
             if constexpr (SPLIT) {
                 // the noise part of this column: second inverse transform where there is one, zeros otherwise (the flag's
@@ -2231,10 +2064,6 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
                     }
                 }
             }
-        }
-        if constexpr (SPLIT && TPREF && NR <= 4 && HGS_SPLIT_L2_PREFETCH) {     // (six slots: no registers to spare)
-#pragma unroll
-            for (int m = 0; m < NR; ++m) asm volatile("" :: "v"(pf_next[m]));
         }
         if (EXTRAS && !FIXED && cp.weights_only) continue;
         if constexpr (BTILE) {
@@ -2278,9 +2107,6 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
 #endif
 }
 
-#ifndef HGS_PRESUM_ABL
-#define HGS_PRESUM_ABL 0     // ablation builds (tools/build_variant.sh): 1 = the pre-pass loads no weights, 2 = neither weights nor targets
-#endif
 template <typename R, int T>
 __device__ __forceinline__ void presum_abl_loads(const R* __restrict__ wc, const R* __restrict__ tc, bool, int j, R (&wr)[16], R (&tr)[16]) {
     static_for<0, 16>([&](auto m_) {
@@ -2462,15 +2288,6 @@ template <typename R, int N, bool PARK = false> constexpr size_t col_tile2_lds_b
            (PARK ? (size_t)6 * Tile2Cfg<N>::T * sizeof(Cx<R>) : 0);
 }
 
-#ifndef HGS_TILE2_BUF_ST
-#define HGS_TILE2_BUF_ST 1   // ... and, in the instances that request the next half tile ahead (NXF), those requests and the stores behind them
-#endif
-#ifndef HGS_TILE2_BUF
-#define HGS_TILE2_BUF 1      // the half tile's rows as straight-line buffer loads (round 6)
-#endif
-#ifndef HGS_TILE2_CONS_GROUP
-#define HGS_TILE2_CONS_GROUP 4      // pixels of a lane whose rule evaluation the scheduler may interleave (168 registers: fewer than col_tile_kernel's 16)
-#endif
 // (4096 rows: three waves per SIMD = three workgroups per CU, the point of the kernel; 2048 rows: two -- the general
 //  transform keeps 20 stage twiddles and up to ten tile slots, at three it spilled 14 .. 103 VGPRs)
 template <typename R, int N, int PHASE, int NR, int RULE, bool PARK = false, bool NXF = false>
@@ -2561,7 +2378,8 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
         //  eight 180.8 -> 175.9 us per column launch; a dense image target 64.3 -> 65.8 us and the 2048-row form 21.2 -> 22.1 us
         //  LOSE -- their constraint / second lane group fills the waits and the resource set-up sits on the chain -- and keep
         //  the conditional loads.)
-        constexpr bool TBUF = HGS_TILE2_BUF && N == 4096 && PHASE == 0 && (NXF || !PARK);
+        constexpr bool TBUF = N == 4096 && PHASE == 0 && (NXF || !PARK);
+        static_assert(!NXF || TBUF, "col_tile2_kernel: the instances that request the next half tile ahead take the buffer form");
         float4 tq[TBUF ? NR : 1];
         if constexpr (TBUF) {
             // (rows that already arrived in nq: an empty resource -- nothing is fetched)
@@ -2622,12 +2440,10 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
             // PHASE 2: the lane's sixteen stored phases (64 contiguous bytes) in two 16-byte registers that are refilled as they
             // are used up -- pixels 0-3 / 8-11 from qa, 4-7 / 12-15 from qb -- instead of sixteen live values (the update
             // instances were 8 .. 12 registers over the 168 of three workgroups per CU)
-            constexpr bool PFQ = PHASE == 2 && HGS_LANE_MAJOR;
+            constexpr bool PFQ = PHASE == 2;
             const float4* pq = PFQ ? reinterpret_cast<const float4*>(pfc + lane_pos<T>(j, 0)) : nullptr;
             float4 qa = make_float4(0, 0, 0, 0), qb = qa;
-            R pf2[(PHASE == 2 && !PFQ) ? 16 : 1];
             if constexpr (PFQ) { qa = pq[0]; qb = pq[1]; }
-            else if constexpr (PHASE == 2) static_for<0, 16>([&](auto m_) { constexpr int m = m_; pf2[m] = pfc[lane_pos<T>(j, m)]; });
             static_for<0, 16>([&](auto m_) {
                 constexpr int m = m_;
                 if constexpr (PFQ && m == 4) qa = pq[2];            // (pixels 0-3 are through)
@@ -2637,9 +2453,9 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                     const float4 qv = ((m / 4) & 1) ? qb : qa;
                     // (pixels 4-7 read qb = pq[1], 8-11 qa = pq[2], 12-15 qb = pq[3])
                     pfm = (m % 4 == 0) ? qv.x : (m % 4 == 1) ? qv.y : (m % 4 == 2) ? qv.z : qv.w;
-                } else if constexpr (PHASE == 2) pfm = pf2[m];
+                }
                 // wave-uniform skip where weight and target are zero (see col_tile_kernel)
-                if (PHASE != 1 && HGS_SPARSE_SKIP && __builtin_amdgcn_ballot_w64(wr[m] != (R)0 || tr[m] != (R)0) == 0) {
+                if (PHASE != 1 && __builtin_amdgcn_ballot_w64(wr[m] != (R)0 || tr[m] != (R)0) == 0) {
                     v[m] = mk<R>(0, 0);
                     return;
                 }
@@ -2721,7 +2537,7 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 outq[m] = make_float4(h0.x, h0.y, h1.x, h1.y);
             }
             have_nq = NXF && ct + ct_step < ntiles;
-            if constexpr (TBUF && NXF && HGS_TILE2_BUF_ST) {
+            if constexpr (NXF) {
                 // straight-line: NR loads through a resource that is empty when there is no next half tile, then NR stores through
                 // one that drops rows outside the SLM -- the compiler can count what is in flight, so the wait for the new rows at
                 // the top of the loop is vmcnt(NR), not vmcnt(0): it no longer includes the acknowledgement of these stores
@@ -2735,20 +2551,11 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 for (int m = 0; m < NR; ++m)
                     bs.template st<float4>(outq[m], (unsigned)(r_lane + m * T) * 4u * (unsigned)sizeof(Cx<R>), 0u);
             } else {
-            if (NXF && have_nq) {
-                const Cx<R>* ghn = a.gh + (size_t)b * g.Sh * g.Pw + (size_t)(ct + ct_step) * g.Sh * 4 + 2 * half;
 #pragma unroll
                 for (int m = 0; m < NR; ++m) {
                     const int r = r_lane + m * T;
-                    nq[NXF ? m : 0] = make_float4(0, 0, 0, 0);
-                    if (r >= 0 && r < g.Sh) nq[NXF ? m : 0] = *reinterpret_cast<const float4*>(ghn + (unsigned)r * 4u);
+                    if (r >= 0 && r < g.Sh) *reinterpret_cast<float4*>(gh + (unsigned)r * 4u) = outq[m];
                 }
-            }
-#pragma unroll
-            for (int m = 0; m < NR; ++m) {
-                const int r = r_lane + m * T;
-                if (r >= 0 && r < g.Sh) *reinterpret_cast<float4*>(gh + (unsigned)r * 4u) = outq[m];
-            }
             }
         }
     }

@@ -2,9 +2,40 @@
 // translation units (launch_row_*.hip / launch_col_*.hip) so hipcc can build them in parallel.
 #pragma once
 #include "kernels.hpp"
+#include "bluestein.hpp"
 #include "dispatch.hpp"
 
 namespace hgs {
+
+// kernel family tag (dispatch.hpp) -> kernel template
+template <typename Fam> struct KernelOf;
+#define HGS_BIND(tag, kernel) \
+    template <> struct KernelOf<tag> { template <typename R, auto... V> static auto ptr() { return kernel<R, V...>; } }
+HGS_BIND(KRow, row_kernel);
+HGS_BIND(KCol, col_kernel);
+HGS_BIND(KFused, col_fused_kernel);
+HGS_BIND(KTile, col_tile_kernel);
+HGS_BIND(KTile2, col_tile2_kernel);
+HGS_BIND(KPresum, col_presum_kernel);
+HGS_BIND(KBlue, bluestein_lines);
+#undef HGS_BIND
+
+// Launches instance <R, V...> of family Fam and notes exactly that instance in the dispatch record: the kernel and the
+// recorded site come from the same argument pack, so the record cannot name another instance than the one that ran.  V
+// names EVERY template argument of the kernel after R (also those it has defaults for): DispatchLog::text() pairs the
+// values with the family's parameter names.  `lds`: dynamic LDS in bytes; above 48 KB the kernel is allowed that much
+// first.  Returns hipError_t as int.
+template <typename Fam, typename R, auto... V, typename... Args>
+static inline int launch_instance(dim3 grid, dim3 block, size_t lds, hipStream_t s, unsigned flags, const Args&... args) {
+    auto k = KernelOf<Fam>::template ptr<R, V...>();
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    dispatch_note(dispatch_site<Fam, R, V...>(), flags);
+    hipLaunchKernelGGL(k, grid, block, lds, s, args...);
+    return (int)hipGetLastError();
+}
 
 template <typename R> inline unsigned row_flags(dim3 grid, const RowArgs<R>& a) {
     return (a.load_mask ? DF_LOAD_MASK : 0u) | (a.store_mask ? DF_STORE_MASK : 0u) | (grid.y > 1 ? DF_BATCH : 0u) | (a.nf_out ? DF_NF_OUT : 0u);

@@ -1,19 +1,11 @@
 // Included by launch_blue_f32.hip / launch_blue_f64.hip with HGS_REAL defined.
-#include "bluestein.hpp"
-#include "dispatch.hpp"
+#include "launch.hpp"
 
 namespace hgs {
 
 template <typename R, int M> static int launch_blue_one(dim3 grid, hipStream_t s, const BlueArgs<R>& a) {
     constexpr size_t lds = (size_t)lds_elems<M>() * sizeof(Cx<R>);
-    auto k = bluestein_lines<R, M>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dispatch_note(dispatch_site<KBlue, R, M>(), grid.y > 1 ? DF_BATCH : 0u);
-    hipLaunchKernelGGL(k, grid, dim3(M / 16), lds, s, a);
-    return (int)hipGetLastError();
+    return launch_instance<KBlue, R, M>(grid, dim3(M / 16), lds, s, grid.y > 1 ? DF_BATCH : 0u, a);
 }
 
 template <> int launch_bluestein<HGS_REAL>(int M, dim3 grid, hipStream_t s, const BlueArgs<HGS_REAL>& a) {

@@ -6,15 +6,7 @@ namespace hgs {
 template <typename R, int N, int MODE>
 static int launch_col_one(dim3 grid, hipStream_t s, const ColArgs<R>& a) {
     constexpr size_t lds = (size_t)ColCfg<N>::CPAR * lds_elems<N>() * sizeof(Cx<R>) + 16 * sizeof(double);
-    auto k = col_kernel<R, N, MODE>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dispatch_note(dispatch_site<KCol, R, N, MODE>(), col_flags(grid, a));
-    hipLaunchKernelGGL(k, grid, dim3(ColCfg<N>::WG), lds, s, a);
-    return (int)hipGetLastError();
+    return launch_instance<KCol, R, N, MODE>(grid, dim3(ColCfg<N>::WG), lds, s, col_flags(grid, a), a);
 }
 
 template <typename R, int N>

@@ -32,15 +32,7 @@ constexpr bool kExtras = HGS_TILE_EXTRAS_TU != 0;
 template <typename R, int N, int PHASE, int NRS = 16>
 static int launch_fused_one(dim3 grid, hipStream_t s, const ColArgs<R>& a) {
     constexpr size_t lds = (size_t)ColCfg<N>::CPAR * lds_elems<N>() * sizeof(Cx<R>) + SCRATCH_DOUBLES * sizeof(double) + fused_ltw_bytes<R, N>();
-    auto k = col_fused_kernel<R, N, PHASE, kStats, 0, NRS>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dispatch_note(dispatch_site<KFused, R, N, PHASE, kStats, 0, NRS>(), col_flags(grid, a));
-    hipLaunchKernelGGL(k, grid, dim3(ColCfg<N>::WG), lds, s, a);
-    return (int)hipGetLastError();
+    return launch_instance<KFused, R, N, PHASE, kStats, 0, NRS>(grid, dim3(ColCfg<N>::WG), lds, s, col_flags(grid, a), a);
 }
 
 template <typename R, int N>
@@ -89,15 +81,7 @@ template <> int LAUNCH_FUSED<HGS_REAL>(int N, int phase, dim3 grid, hipStream_t 
 template <int N, int PHASE>
 static int launch_tile_one(dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {
     constexpr size_t lds = col_tile_lds_bytes<float, N>();
-    auto k = col_tile_kernel<float, N, PHASE, 6, kStats, kExtras>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dispatch_note(dispatch_site<KTile, float, N, PHASE, 6, kStats, kExtras, 0, -1>(), col_flags(grid, a));
-    hipLaunchKernelGGL(k, grid, dim3(N / 16), lds, s, a, m0);
-    return (int)hipGetLastError();
+    return launch_instance<KTile, float, N, PHASE, 6, kStats, kExtras, 0, -1>(grid, dim3(N / 16), lds, s, col_flags(grid, a), a, m0);
 }
 
 template <> int LAUNCH_TILE<float>(int N, int phase, dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {

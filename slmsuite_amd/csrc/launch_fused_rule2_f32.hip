@@ -7,14 +7,7 @@ namespace hgs {
 template <int N, int PHASE>
 static int launch_fused_rule2_one(dim3 grid, hipStream_t s, const ColArgs<float>& a) {
     constexpr size_t lds = (size_t)ColCfg<N>::CPAR * lds_elems<N>() * sizeof(Cx<float>) + SCRATCH_DOUBLES * sizeof(double);
-    auto k = col_fused_kernel<float, N, PHASE, false, 2>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dispatch_note(dispatch_site<KFused, float, N, PHASE, false, 2, 16>(), col_flags(grid, a));
-    hipLaunchKernelGGL(k, grid, dim3(ColCfg<N>::WG), lds, s, a);
-    return (int)hipGetLastError();
+    return launch_instance<KFused, float, N, PHASE, false, 2, 16>(grid, dim3(ColCfg<N>::WG), lds, s, col_flags(grid, a), a);
 }
 template <int N> static int launch_fused_rule2_n(int phase, dim3 grid, hipStream_t s, const ColArgs<float>& a) {
     if (phase == 0) return launch_fused_rule2_one<N, 0>(grid, s, a);

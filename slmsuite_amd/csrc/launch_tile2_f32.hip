@@ -7,14 +7,8 @@ namespace hgs {
 template <int N, int PHASE, int RULE, int NR, bool PARK = false, bool NXF = false>
 static int launch_tile2_one(dim3 grid, hipStream_t s, const ColArgs<float>& a, int shift, int half_xmap) {
     constexpr size_t lds = col_tile2_lds_bytes<float, N, PARK>();
-    auto k = col_tile2_kernel<float, N, PHASE, NR, RULE, PARK, NXF>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dispatch_note(dispatch_site<KTile2, float, N, PHASE, NR, RULE, PARK, NXF>(), col_flags(grid, a) | (half_xmap ? DF_XMAP : 0u));
-    hipLaunchKernelGGL(k, grid, dim3(Tile2Cfg<N>::WG), lds, s, a, shift, half_xmap);
-    return (int)hipGetLastError();
+    return launch_instance<KTile2, float, N, PHASE, NR, RULE, PARK, NXF>(grid, dim3(Tile2Cfg<N>::WG), lds, s,
+                                                                         col_flags(grid, a) | (half_xmap ? DF_XMAP : 0u), a, shift, half_xmap);
 }
 template <int N, int RULE, int NR>
 static int launch_tile2_n(int phase, dim3 grid, hipStream_t s, const ColArgs<float>& a, int shift, int half_xmap) {

@@ -8,12 +8,7 @@ namespace hgs {
 template <int N, int PHASE, int NR, int RULE>
 static int launch_tile_presum_one(dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {
     constexpr size_t lds = col_tile_lds_bytes<float, N>();
-    auto k = col_tile_kernel<float, N, PHASE, NR, false, true, RULE>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    dispatch_note(dispatch_site<KTile, float, N, PHASE, NR, false, true, RULE, -1>(), col_flags(grid, a));
-    hipLaunchKernelGGL(k, grid, dim3(N / 16), lds, s, a, m0);
-    return (int)hipGetLastError();
+    return launch_instance<KTile, float, N, PHASE, NR, false, true, RULE, -1>(grid, dim3(N / 16), lds, s, col_flags(grid, a), a, m0);
 }
 // rule 5: the update behind its pre-pass (a.dpartial set); rule 6: MRAF without a weight update
 template <int N, int NR>
@@ -47,12 +42,7 @@ int launch_tile_presum(int N, int phase, int nr, dim3 grid, hipStream_t s, const
 template <int N, int NR>
 static int launch_presum_one(dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {
     constexpr size_t lds = col_presum_lds_bytes<float, N>();
-    auto k = col_presum_kernel<float, N, NR>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    dispatch_note(dispatch_site<KPresum, float, N, NR>(), col_flags(grid, a));
-    hipLaunchKernelGGL(k, grid, dim3(N / 16), lds, s, a, m0);
-    return (int)hipGetLastError();
+    return launch_instance<KPresum, float, N, NR>(grid, dim3(N / 16), lds, s, col_flags(grid, a), a, m0);
 }
 
 // the pre-pass: a.col_flags (column scan) required, a.wpartial = where the partials go (one per workgroup and hologram)

@@ -16,14 +16,7 @@ namespace hgs {
 template <int N, int PHASE, int RULE, int NR>
 static int launch_tile_rule_one(dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {
     constexpr size_t lds = col_tile_lds_bytes<float, N>();
-    auto k = col_tile_kernel<float, N, PHASE, NR, false, false, RULE, HGS_TILE_LISTED>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dispatch_note(dispatch_site<KTile, float, N, PHASE, NR, false, false, RULE, HGS_TILE_LISTED>(), col_flags(grid, a));
-    hipLaunchKernelGGL(k, grid, dim3(N / 16), lds, s, a, m0);
-    return (int)hipGetLastError();
+    return launch_instance<KTile, float, N, PHASE, NR, false, false, RULE, HGS_TILE_LISTED>(grid, dim3(N / 16), lds, s, col_flags(grid, a), a, m0);
 }
 template <int N, int RULE, int NR>
 static int launch_tile_rule_n(int phase, dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {

@@ -16,12 +16,8 @@ namespace hgs {
 template <int N, int PHASE, int NR, int RULE>
 static int launch_tile_split_one(dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {
     constexpr size_t lds = col_tile_split_lds_bytes<float, N>();
-    auto k = col_tile_kernel<float, N, PHASE, NR, HGS_SPLIT_STATS != 0, true, RULE>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    dispatch_note(dispatch_site<KTile, float, N, PHASE, NR, HGS_SPLIT_STATS != 0, true, RULE, -1>(), col_flags(grid, a));
-    hipLaunchKernelGGL(k, grid, dim3(N / 16), lds, s, a, m0);
-    return (int)hipGetLastError();
+    static_assert(lds > 48 * 1024, "launch_tile_split_one: image + parked noise part need the raised LDS limit");
+    return launch_instance<KTile, float, N, PHASE, NR, HGS_SPLIT_STATS != 0, true, RULE, -1>(grid, dim3(N / 16), lds, s, col_flags(grid, a), a, m0);
 }
 template <int N, int NR, int RULE>
 static int launch_tile_split_r(int phase, dim3 grid, hipStream_t s, const ColArgs<float>& a, int m0) {
@@ -54,14 +50,7 @@ int LAUNCH_TILE_SPLIT(int N, int phase, int nr, int rule_ok, dim3 grid, hipStrea
 template <int N, int MODE, int NS>
 static int launch_row_split_one(dim3 grid, hipStream_t s, const RowArgs<float>& a) {
     constexpr size_t lds = (size_t)RowCfg<N>::FPW * lds_elems<N>() * sizeof(Cx<float>);
-    auto k = row_kernel<float, N, MODE, NS, false, true>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    dispatch_note(dispatch_site<KRow, float, N, MODE, NS, false, true>(), row_flags(grid, a));
-    hipLaunchKernelGGL(k, grid, dim3(RowCfg<N>::WG), lds, s, a);
-    return (int)hipGetLastError();
+    return launch_instance<KRow, float, N, MODE, NS, false, true>(grid, dim3(RowCfg<N>::WG), lds, s, row_flags(grid, a), a);
 }
 template <int N>
 static int launch_row_split_n(int mode, dim3 grid, hipStream_t s, const RowArgs<float>& a) {
