@@ -118,8 +118,10 @@ enum {
     HGS_MONOMIALS = 15,   /* int32 [n_monomials][2] (px, py)   phase._zernike_get_cantor terms; the pseudo-term
                              (-1, 0) is the vortex plate w * atan2(y, x), w > 0 only (phase.py:1783-1790)     */
     HGS_SPOT_COEFF = 16,  /* real [n_monomials][n_spots]       ... and weights (phase.py:850-920)    */
-    HGS_PHASE_PREV = 17   /* get only: [batch][slm_h][slm_w] real -- the phase the last one-iteration hgs_iterate call
+    HGS_PHASE_PREV = 17,  /* get only: [batch][slm_h][slm_w] real -- the phase the last one-iteration hgs_iterate call
                              STARTED from (HGS_OPT_KEEP_PREV_PHASE); HGS_ERR_STATE when none is held */
+    HGS_CG_GRAD = 18      /* get only: [slm_h][slm_w] real -- dL/dphase of the last hgs_cg_iterate body that kept it
+                             (hgs_cg_params.keep_grad); HGS_ERR_STATE before the first such body */
 };
 
 int hgs_create(const hgs_config* cfg, hgs_engine** out);
@@ -180,6 +182,28 @@ int hgs_stats(hgs_engine* e, int group, int width, const double* spot_xy_float, 
  * otherwise the call runs the general path with a hgs_stats per iteration. */
 int hgs_iterate_stats(hgs_engine* e, hgs_step* step, int n_iter, uint8_t* fixed_phase_history,
                       int stat_groups, int width, const double* spot_xy_float, double* stats_out);
+
+/* Hologram.optimize_cg (_hologram.py:1664-1759) with the reference's defaults: loss ComplexMSELoss (:6-14, mean reduction),
+ * optimizer torch.optim.Adam without weight decay or amsgrad, feedback "computational".  No autograd: the loss
+ *     L = (1 / M) sum_k (|F_k| / ||F|| - t_k)^2,   F = the farfield of amp * exp(i (phase + propagation_kernel)),  M = pad_h * pad_w
+ * has the closed-form gradient dL/dphase = Im(conj(n) g), n the nearfield and g the inverse transform of
+ * (2 / (M ||F||)) (|F| / ||F|| - t) F / |F| over the SLM window (the term through ||F|| vanishes: the transform is unitary and
+ * ||n|| does not depend on the phase).  One body is hgs_nearfield2farfield, an element-wise pass over the farfield, the
+ * inverse transform without phase extraction and an element-wise Adam update over the SLM window
+ *     m <- beta1 m + (1 - beta1) g,   v <- beta2 v + (1 - beta2) g^2,
+ *     phase <- phase - (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps),     t = 1, 2, ...
+ * The phase is not wrapped.  The engine keeps m, v and t between calls; `restart` zeroes them first (the reference builds a
+ * new optimizer in every optimize() call), and so does hgs_reset, after which HGS_CG_GRAD is not held either.  Weights, phase_ff and the statistics are untouched; the farfield buffer is
+ * consumed (hgs_nearfield2farfield rebuilds it from the new phase).  The target must not hold NaN (the loss would be NaN). */
+typedef struct {
+    double lr, beta1, beta2, eps;
+    int32_t restart;     /* != 0: zero m, v and t before the first body                                   */
+    int32_t keep_grad;   /* != 0: every body also stores its gradient for hgs_get_array(HGS_CG_GRAD)       */
+} hgs_cg_params;
+/* n_iter bodies without a host synchronisation in between; loss_out[n_iter] (optional) receives the loss each body
+ * evaluated, i.e. that of the phase it STARTED from (flags["loss_result"], :1714).  kind 0 and batch 1 only
+ * (HGS_ERR_UNSUPPORTED otherwise); power-of-two and general padded shapes alike. */
+int hgs_cg_iterate(hgs_engine* e, const hgs_cg_params* params, int n_iter, double* loss_out);
 
 /* MultiplaneHologram._farfield2nearfield (_multiplane.py:255-279): every child runs
  * _farfield2nearfield(extract=False) on its own (constrained) farfield; the children's complex
@@ -243,9 +267,12 @@ int hgs_set_option(hgs_engine* e, int option, int value);
 
 /* Timing support for bench.py: per-kernel HIP-event timing on the engine stream. */
 enum { HGS_K_ROW = 0, HGS_K_COL_FUSED = 1, HGS_K_COL_FWD = 2, HGS_K_COL_INV = 3, HGS_K_ELEMENTWISE = 4,
-       HGS_K_COUNT = 5 };
+       HGS_K_CG_SEED = 5 /* cg_seed_kernel + its loss reduction */, HGS_K_CG_ADAM = 6 /* cg_adam_kernel */,
+       HGS_K_COUNT = 7 };
 int hgs_profile_enable(hgs_engine* e, int on);
-/* out[HGS_K_COUNT][2] = {total milliseconds, launches} since the last call; syncs the stream */
+/* out[HGS_K_COUNT][2] = {total milliseconds, launches} since the last call; syncs the stream.  The table grew from 5 to
+ * 7 rows with hgs_cg_iterate: a caller sizes its buffer by HGS_K_COUNT of the header it was BUILT against, so one built
+ * against the five-row header must be rebuilt before it runs on this library (version "hgs 0.2") */
 int hgs_profile_read(hgs_engine* e, double* out);
 /* elapsed milliseconds of hgs_iterate(step, n_iter) measured with a HIP event pair on the engine
  * stream (SURVEY 8d timing protocol) */
@@ -256,8 +283,8 @@ int hgs_iterate_timed(hgs_engine* e, hgs_step* step, int n_iter, double* ms);
  *     "col_tile_kernel<R=float,N=4096,PHASE=0,NR=6,STATS=false,EXTRAS=false,RULE=1,LISTED=0> xmap\t50\n"
  * (family, its template arguments by name -- the ones rocprofv3 prints positionally --, flags list / load_mask /
  * store_mask / xmap / batch / stats / nf_out, launch count).  Families: row_kernel, col_kernel, col_fused_kernel,
- * col_tile_kernel, bluestein_lines, c_n2f_run, c_f2n_run, c_n2f_partial, c_f2n, cgemm_streamk (the small element-wise /
- * reduction helpers are not recorded).  The tests assert it next to the numbers: neighbouring variants often agree to
+ * col_tile_kernel, bluestein_lines, c_n2f_run, c_f2n_run, c_n2f_partial, c_f2n, cgemm_streamk, cg_seed_kernel, cg_adam_kernel
+ * (the small element-wise / reduction helpers are not recorded).  The tests assert it next to the numbers: neighbouring variants often agree to
  * the last bit, so only this shows that a policy reached the kernel it names.  `needed` (optional) receives the bytes
  * the text takes including the terminator; with buf = NULL and nbytes = 0 the call is a size query and keeps the record,
  * otherwise a buffer that is too small fails with HGS_ERR_ARG (record kept) and success clears the record. */

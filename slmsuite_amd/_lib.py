@@ -21,8 +21,9 @@ OPT_KEEP_PREV_PHASE = 8
 (PHASE, AMP, AMP_SCALAR, PROP_KERNEL, TARGET, WEIGHTS, PHASE_FF, FARFIELD, AMP_FF, SPOT_INDEX,
  SPOT_AMP, EXTERNAL_AMP, ZERO_WEIGHTS, XGRID, YGRID, MONOMIALS, SPOT_COEFF) = range(17)
 PHASE_PREV = 17
+CG_GRAD = 18
 FB_PIXEL, FB_SPOT_WINDOW, FB_EXTERNAL = 0, 1, 2
-K_NAMES = ("row", "col_fused", "col_fwd", "col_inv", "elementwise")
+K_NAMES = ("row", "col_fused", "col_fwd", "col_inv", "elementwise", "cg_seed", "cg_adam")
 
 
 class hgs_config(C.Structure):
@@ -36,6 +37,10 @@ class hgs_step(C.Structure):
                  "mraf_enabled", "has_mraf_factor", "zero_mode", "spot_window", "efficiency_group", "reserved")] + \
                [(n, C.c_double) for n in
                 ("feedback_exponent", "feedback_factor", "mraf_factor", "zero_factor", "fix_phase_efficiency")]
+
+
+class hgs_cg_params(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps")] + [(n, C.c_int32) for n in ("restart", "keep_grad")]
 
 
 _lib = None
@@ -103,6 +108,7 @@ def load():
         "hgs_multiplane_farfield2nearfield": (C.c_int, [P(eng), P(C.c_double), C.c_int]),
         "hgs_iterate_stats": (C.c_int, [eng, P(hgs_step), C.c_int, P(C.c_uint8), C.c_int, C.c_int,
                                         P(C.c_double), P(C.c_double)]),
+        "hgs_cg_iterate": (C.c_int, [eng, P(hgs_cg_params), C.c_int, P(C.c_double)]),
         "hgs_sync": (C.c_int, [eng]),
         "hgs_set_option": (C.c_int, [eng, C.c_int, C.c_int]),
         "hgs_profile_enable": (C.c_int, [eng, C.c_int]),
@@ -122,7 +128,7 @@ def load():
 
 EXPORTS = ("hgs_create", "hgs_destroy", "hgs_set_array", "hgs_get_array", "hgs_get_array_device", "hgs_set_array_device", "hgs_copy_phase",
            "hgs_reset_weights", "hgs_reset", "hgs_set_array_sparse", "hgs_nearfield2farfield", "hgs_farfield_constraint",
-           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
+           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_cg_iterate", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
            "hgs_profile_read", "hgs_iterate_timed", "hgs_dispatch_read", "hgs_last_error", "hgs_version")
 
 

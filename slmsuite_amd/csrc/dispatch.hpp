@@ -65,6 +65,8 @@ HGS_FAMILY(KCf2nRun, "c_f2n_run", "R,DEG");
 HGS_FAMILY(KCn2fPix, "c_n2f_partial", "R,DEG");
 HGS_FAMILY(KCf2nPix, "c_f2n", "R,DEG");
 HGS_FAMILY(KCgemm, "cgemm_streamk", "R,EPI");
+HGS_FAMILY(KCgSeed, "cg_seed_kernel", "R");
+HGS_FAMILY(KCgAdam, "cg_adam_kernel", "R");
 #undef HGS_FAMILY
 
 }  // namespace hgs

@@ -19,6 +19,7 @@
 #include "cgemm.hpp"
 #include "compressed_sep.hpp"
 #include "bluestein.hpp"
+#include "cg_kernels.hpp"
 #include <complex>
 #include <dlfcn.h>
 
@@ -161,6 +162,7 @@ struct EngineBase {
     virtual int profile_enable(int on) = 0;
     virtual int profile_read(double* out) = 0;
     virtual int iterate_timed(hgs_step* st, int n, double* ms) = 0;
+    virtual int cg_iterate(const hgs_cg_params* p, int n, double* loss_out) = 0;
 };
 
 template <typename R> struct Engine : EngineBase {
@@ -229,6 +231,15 @@ template <typename R> struct Engine : EngineBase {
     R* phase_prev = nullptr;
     bool have_prev = false;
     int opt_prev_phase = 0;
+    // hgs_cg_iterate (optimize(method="CG")): Adam moments and the last gradient over the SLM window, the partial sums of the
+    // seed pass and one loss per body of the running call; all allocated by the first call.  cg_t: Adam's step counter
+    R* cg_m = nullptr;
+    R* cg_v = nullptr;
+    R* cg_grad = nullptr;
+    double* cg_partial = nullptr;      // [ew_blocks]
+    double* cg_loss = nullptr;         // [cg_loss_cap] sum r^2 of each body
+    int cg_loss_cap = 0, cg_t = 0;
+    bool cg_have_grad = false;
     // per-column kernel (float64; float32 where the tile-resident kernel does not run) single-pass MRAF: noise part as farfield
     // values, the columns that hold it, their inverse pass
     C* ffb = nullptr;                      // [B][P], layout of ff; only NaN-target pixels are ever written, the rest stays zero
@@ -315,7 +326,7 @@ template <typename R> struct Engine : EngineBase {
     ~Engine() override {
         if (stream) hipStreamSynchronize(stream);
         if (tw_col == tw_row) tw_col = nullptr;
-        void* ptrs[] = {phase_prev, ffb, col_list_signal, n_signal_dev, col_list_noise, n_noise_dev, lane_mask_tmp, lane_mask_noise, phase, amp, kern, gh, gh2, w, t, pff, ff, aff, zw, staging, tw_row, tw_col, wpartial, dpartial,
+        void* ptrs[] = {cg_m, cg_v, cg_grad, cg_partial, cg_loss, phase_prev, ffb, col_list_signal, n_signal_dev, col_list_noise, n_noise_dev, lane_mask_tmp, lane_mask_noise, phase, amp, kern, gh, gh2, w, t, pff, ff, aff, zw, staging, tw_row, tw_col, wpartial, dpartial,
                         fpartial, epartial, sums, wscale, spot_xy, spot_amp, ext_amp, spot_fb, nfbuf, nog_dev, stats_scratch, stats_dxy, col_active, sig_rows, col_list, n_active_dev, lane_mask, col_active_d, col_list_d, n_active_d_dev, lane_mask_d, stat_partial, stat_tsum, xg, yg, mono, coeff, cpartial, cnorm, ext_r, sep_c, sep_g, sep_ex, sep_exT, sep_ey, sep_nfT, sep_b2, sep_c1, sep_c2, sep_norm, run_rec, run_ys, run_nf, sk_tab};
         for (void* p : ptrs)
             if (p) hipFree(p);
@@ -1352,6 +1363,13 @@ template <typename R> struct Engine : EngineBase {
                 HIPCHK(hipStreamSynchronize(stream));
                 return 0;
             }
+            case HGS_CG_GRAD: {
+                if (!cg_grad || !cg_have_grad) return fail(HGS_ERR_STATE, "no gradient is held (hgs_cg_iterate with keep_grad has not run)");
+                if (nbytes != S * sizeof(R)) return fail(HGS_ERR_ARG, "gradient: bad size %zu", nbytes);
+                HIPCHK(hipMemcpyAsync(dst, cg_grad, nbytes, dst_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                return 0;
+            }
             case HGS_TARGET: return download_T<R>(t, dst, nbytes, dst_device, nullptr);
             case HGS_WEIGHTS: return download_T<R>(w, dst, nbytes, dst_device, w_pending ? wscale : nullptr);
             case HGS_PHASE_FF:
@@ -1382,6 +1400,8 @@ template <typename R> struct Engine : EngineBase {
         have_prev = false;
         farfield_valid = false;
         gh_state = -1;          // (a kept G is the un-extracted phasor of the last body: a reset hologram starts from its phase, like a new one)
+        cg_t = 0;               // Adam starts over (hgs_cg_iterate zeroes the moments at step 0) and no gradient is held
+        cg_have_grad = false;
         return reset_weights();
     }
     // n values at listed pixels, `0` everywhere else (SpotHologram targets: n_spots numbers instead of P)
@@ -1723,6 +1743,72 @@ template <typename R> struct Engine : EngineBase {
             return 0;
         });
     }
+    // n bodies of Hologram.optimize_cg (:1704-1735) with the default loss and Adam (include/hgs.h, cg_kernels.hpp).  Both
+    // transforms are the engine's own, unchanged: n2f leaves F and sum |F|^2 on the device, the seed pass turns F into the
+    // adjoint seed in place, f2n_complex brings it back over the SLM window, the Adam pass forms the gradient and moves
+    // the phase.  Nothing is read by the host until the loop is over.
+    int cg_iterate(const hgs_cg_params* p, int n, double* loss_out) override {
+        RoctxRange range(opt_roctx, "hgs_cg_iterate");
+        if (cfg.kind != 0) return fail(HGS_ERR_UNSUPPORTED, "hgs_cg_iterate: padded-grid holograms only (engine kind 0)");
+        if (B != 1) return fail(HGS_ERR_UNSUPPORTED, "hgs_cg_iterate: one hologram per engine (batch is %d)", B);
+        if (n < 0) return fail(HGS_ERR_ARG, "hgs_cg_iterate: n_iter must be >= 0");
+        if (!(p->lr >= 0) || !std::isfinite(p->lr)) return fail(HGS_ERR_ARG, "Invalid learning rate: %g", p->lr);
+        if (!(p->eps >= 0) || !std::isfinite(p->eps)) return fail(HGS_ERR_ARG, "Invalid epsilon value: %g", p->eps);
+        if (!(p->beta1 >= 0 && p->beta1 < 1)) return fail(HGS_ERR_ARG, "Invalid beta parameter at index 0: %g", p->beta1);
+        if (!(p->beta2 >= 0 && p->beta2 < 1)) return fail(HGS_ERR_ARG, "Invalid beta parameter at index 1: %g", p->beta2);
+        if (!has_target) return fail(HGS_ERR_STATE, "target has not been set");
+        // (each buffer on its own pointer: a call that failed half way allocates the rest next time.  The moments are
+        //  zeroed by whoever starts Adam: a restart, or -- cg_t == 0 -- a first call and the first one after hgs_reset)
+        if (!cg_m) { if (dalloc(&cg_m, S)) return HGS_ERR_DEVICE; cg_t = 0; }
+        if (!cg_v) { if (dalloc(&cg_v, S)) return HGS_ERR_DEVICE; cg_t = 0; }
+        if (!cg_partial) { if (dalloc(&cg_partial, (size_t)ew_blocks)) return HGS_ERR_DEVICE; }
+        if (p->restart) cg_t = 0;
+        if (cg_t == 0) {
+            HIPCHK(hipMemsetAsync(cg_m, 0, S * sizeof(R), stream));
+            HIPCHK(hipMemsetAsync(cg_v, 0, S * sizeof(R), stream));
+        }
+        if (p->keep_grad && !cg_grad) { if (dalloc(&cg_grad, S)) return HGS_ERR_DEVICE; }
+        if (n == 0) return 0;
+        if (cg_loss_cap < n) {
+            if (cg_loss) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(cg_loss)); cg_loss = nullptr; cg_loss_cap = 0; }
+            if (dalloc(&cg_loss, (size_t)n)) return HGS_ERR_DEVICE;
+            cg_loss_cap = n;
+        }
+        for (int it = 0; it < n; ++it) {
+            if (int e = n2f(0)) return e;
+            int r = timed(HGS_K_CG_SEED, [&]() -> int {
+                CgSeedArgs<R> a{};
+                a.ff = ff; a.t = t; a.fsum = sums + 0 * B; a.partial = cg_partial; a.P = P;
+                LCHK(launch_cg_seed<R>(ew_blocks, stream, a));
+                return reduce(cg_partial, ew_blocks, cg_loss + it);
+            });
+            if (r) return r;
+            // (ff holds the seed now; farfield_valid stays set for the inverse, which clears it -- and gh_state with it)
+            if (int e = f2n_complex()) return e;
+            ++cg_t;
+            r = timed(HGS_K_CG_ADAM, [&]() -> int {
+                CgAdamArgs<R> a{};
+                a.g = nfbuf; a.phase = phase; a.amp = has_amp ? amp : nullptr; a.kern = has_kern ? kern : nullptr;
+                a.m = cg_m; a.v = cg_v; a.grad = p->keep_grad ? cg_grad : nullptr;
+                a.amp_scalar = (R)amp_scalar; a.beta1 = (R)p->beta1; a.beta2 = (R)p->beta2; a.eps = (R)p->eps;
+                a.step_size = (R)(p->lr / (1.0 - std::pow(p->beta1, (double)cg_t)));
+                a.inv_bc2_sqrt = (R)(1.0 / std::sqrt(1.0 - std::pow(p->beta2, (double)cg_t)));
+                a.S = S;
+                LCHK(launch_cg_adam<R>(stream, a));
+                return 0;
+            });
+            if (r) return r;
+            if (p->keep_grad) cg_have_grad = true;
+        }
+        have_prev = false;      // (HGS_PHASE_PREV described the phase a fused body started from: it is no longer the previous one)
+        if (loss_out) {
+            HIPCHK(hipMemcpyAsync(loss_out, cg_loss, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            for (int it = 0; it < n; ++it) loss_out[it] /= (double)P;      // mean reduction
+        }
+        return 0;
+    }
+
     int mp_info(MpInfo* o) override {
         o->nf = nfbuf; o->kern = has_kern ? kern : nullptr; o->phase = phase; o->S = S; o->B = B;
         o->real_bytes = (int)sizeof(R); o->device = cfg.device; o->stream = stream;
@@ -2579,6 +2665,11 @@ int hgs_iterate(hgs_engine* e, hgs_step* step, int n_iter, uint8_t* hist) {
     if (!step) return hgs::fail(HGS_ERR_ARG, "null step");
     return e->impl->iterate(step, n_iter, hist);
 }
+int hgs_cg_iterate(hgs_engine* e, const hgs_cg_params* params, int n_iter, double* loss_out) {
+    ENG(e)
+    if (!params) return hgs::fail(HGS_ERR_ARG, "null parameters");
+    return e->impl->cg_iterate(params, n_iter, loss_out);
+}
 int hgs_iterate_stats(hgs_engine* e, hgs_step* step, int n_iter, uint8_t* hist, int stat_groups, int width,
                       const double* spot_xy_float, double* stats_out) {
     ENG(e)
@@ -2623,7 +2714,7 @@ const char* hgs_last_error(void) { return hgs::g_err.c_str(); }
 const char* hgs_version(void) {
     static std::string v;
     if (v.empty()) {
-        v = "hgs 0.1 gfx950";
+        v = "hgs 0.2 gfx950";
         int n = 0;
         if (hipGetDeviceCount(&n) == hipSuccess && n > 0) {
             hipDeviceProp_t p;

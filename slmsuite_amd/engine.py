@@ -190,6 +190,23 @@ class Engine:
             per_iter.append(d)
         return [bool(hist[i]) for i in range(n_iter)], per_iter
 
+    def cg_iterate(self, n_iter, lr=0.1, betas=(0.9, 0.999), eps=1e-8, restart=False, keep_grad=False):
+        """
+        hgs_cg_iterate: ``n_iter`` bodies of the gradient loop (default loss, Adam) in one call.  Returns the loss each body
+        evaluated -- that of the phase it started from -- as a float64 array.
+        """
+        prm = L.hgs_cg_params(lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps),
+                              restart=int(bool(restart)), keep_grad=int(bool(keep_grad)))
+        out = (C.c_double * max(1, n_iter))()
+        L.check(self.lib.hgs_cg_iterate(self._h, C.byref(prm), int(n_iter), out))
+        return np.array(out[:max(0, n_iter)], dtype=np.float64)
+
+    def get_cg_grad(self):
+        """HGS_CG_GRAD: dL/dphase of the last ``cg_iterate(..., keep_grad=True)`` body, ``slm_shape``."""
+        out = np.empty(self.slm_shape, dtype=self.dtype)
+        L.check(self.lib.hgs_get_array(self._h, L.CG_GRAD, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
     def iterate_timed(self, step, n_iter):
         ms = C.c_double()
         L.check(self.lib.hgs_iterate_timed(self._h, C.byref(step), int(n_iter), C.byref(ms)))

@@ -621,6 +621,12 @@ class Hologram:
         self._calculate_stats_computational(stats, stat_groups)
         self._update_stats_dictionary(stats)
 
+    def _calculate_stats(self, stat_groups):
+        """The statistics ``_update_stats`` would record, not yet recorded (optimize_cg takes them before a body)."""
+        stats = {}
+        self._calculate_stats_computational(stats, stat_groups)
+        return stats
+
     # ---- optimize (_hologram.py:1076-1424) --------------------------------------------------------------------
     def optimize(self, method="GS", maxiter=20, verbose=True, callback=None, feedback=None,
                  stat_groups=[], **kwargs):
@@ -632,8 +638,7 @@ class Hologram:
         if "GS" in method:
             self.optimize_gs(iterations, callback)
         elif "CG" in method:
-            raise NotImplementedError(
-                "'CG' (torch autograd, experimental in the reference) is outside the GS/WGS hot path of this build")
+            self.optimize_cg(iterations, callback)
         else:
             raise ValueError(f"Unsupported optimization method '{method}'")
 
@@ -930,6 +935,119 @@ class Hologram:
                 self.iter += 1
         # _populate_results (:934-949) runs when somebody asks for farfield / amp_ff / phase_ff, when the phase is
         # replaced, or ahead of the next call that depends on it -- not before optimize() returns
+        self._populate_pending = True
+
+    # ---- gradient refinement (_hologram.py:1664-1759) ---------------------------------------------------------------
+    _CG_ADAM_KWARGS = ("lr", "betas", "eps")
+
+    def _cg_settings(self):
+        """
+        Everything ``optimize("CG")`` can refuse without a device: returns the Adam settings for Engine.cg_iterate.  The
+        engine evaluates the reference's DEFAULT loss (ComplexMSELoss, mean reduction) and steps torch's Adam with its
+        defaults (betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad) in closed form -- there is no autograd graph
+        to hang another loss or optimizer on, so those are errors rather than silently something else.
+        """
+        fl = self.flags
+        optimizer = fl.get("optimizer", "Adam")
+        if optimizer != "Adam":
+            raise NotImplementedError(f"optimizer '{optimizer}' is not supported: method 'CG' runs torch.optim.Adam's update "
+                                      "rule on the engine (optimizer='Adam')")
+        if fl.get("loss", None) is not None:
+            raise NotImplementedError("a custom `loss` is not supported: method 'CG' evaluates the default ComplexMSELoss "
+                                      "(loss=None) and its analytic gradient on the engine")
+        fb = fl.get("feedback", "computational")
+        if fb in ("experimental", "experimental_spot"):
+            raise NotImplementedError(f"Feedback '{fb}' needs camera hardware and is outside this build")
+        if fb != "computational":
+            raise ValueError(f"Feedback '{fb}' is not available for method 'CG': its loss compares the computed farfield "
+                             "with the target ('computational')")
+        kwargs = dict(fl.get("optimizer_kwargs", None) or {})
+        unknown = sorted(set(kwargs) - set(self._CG_ADAM_KWARGS))
+        if unknown:
+            raise ValueError(f"optimizer_kwargs {unknown} not supported: the engine's Adam takes {list(self._CG_ADAM_KWARGS)}")
+        betas = tuple(float(b) for b in kwargs.get("betas", (0.9, 0.999)))
+        if len(betas) != 2:
+            raise ValueError("optimizer_kwargs['betas'] must be a pair")
+        if self._mraf_enabled():
+            raise ValueError("the target contains NaN (MRAF noise region): the default loss of method 'CG' would be NaN")
+        return dict(lr=float(kwargs.get("lr", 1e-3)), betas=betas, eps=float(kwargs.get("eps", 1e-8)),
+                    keep_grad=bool(fl.get("keep_gradient", False)))
+
+    def get_cg_gradient(self):
+        """dL/dphase as the last iteration of ``optimize("CG", keep_gradient=True)`` evaluated it, i.e. at the phase that
+        iteration started from (what autograd leaves in ``phase.grad``); ``slm_shape``."""
+        if self._engine is None:
+            raise RuntimeError("no gradient is held: run optimize('CG', keep_gradient=True) first")
+        return self._engine.get_cg_grad()
+
+    def optimize_cg(self, iterations, callback):
+        """
+        ``Hologram.optimize_cg`` (:1664-1759) on the engine: per iteration one forward transform, the adjoint seed of the
+        loss, one inverse transform and the Adam update, all device resident (Engine.cg_iterate).  Adam starts afresh in
+        every call, like the reference's optimizer object.  Without a callback and statistics the loop is one engine call;
+        a callback gets one call per iteration and sees the phase that iteration produced (flag ``keep_gradient``: the
+        gradient too, :meth:`get_cg_gradient`); requested statistics are
+        those of the farfield the iteration evaluates (one more forward transform per iteration -- the reference records
+        a stale ``amp_ff`` here, DESIGN.md "Gradient refinement").
+        """
+        adam = self._cg_settings()
+        self.flags.pop("keep_gradient", None)            # an option of this call, not a flag: it stays out of the history
+        # the results of an earlier call that nobody looked at describe a phase this loop replaces
+        self._populate_pending = False
+        self._stale -= {"farfield", "amp_ff", "phase_ff"}
+        e = self._get_engine()
+        n_total = len(iterations)
+        groups = list(self.flags["stat_groups"])
+        bar = iterations if (tqdm is not None and not isinstance(iterations, range)) else None
+        restart = True
+
+        def bodies(n):
+            nonlocal restart
+            loss = e.cg_iterate(n, restart=restart, **adam)
+            restart = False
+            self._mark_device_fresh(["phase"])
+            self._stale -= {"farfield", "amp_ff"}          # the loop consumed the farfield it evaluated
+            if n > 0:
+                self.flags["loss_result"] = float(loss[-1])
+            return loss
+
+        if callback is None and not groups and not self.flags.get("raw_stats", False):
+            loss = bodies(n_total)
+            self._update_stats_batch(n_total, [self.flags.get("fixed_phase")] * n_total, None, [])
+            if n_total > 0:
+                _history_put(self.stats["flags"].setdefault("loss_result", []), self.iter, [float(v) for v in loss])
+            self.iter += n_total
+            if bar is not None:
+                bar.update(n_total)
+        else:
+            if n_total == 0:
+                bodies(0)
+            raw = self.flags.get("raw_stats", False)
+            for _ in range(n_total):
+                e = self._get_engine()                   # push what a callback changed
+                stats, frame = {}, None
+                if groups or raw:
+                    # the body consumes the farfield it evaluates: its statistics are taken from one more transform first
+                    self._populate_pending = False
+                    e.nearfield2farfield(store_phase_ff=False)
+                    self._mark_device_fresh(["farfield", "amp_ff"])
+                    stats = self._calculate_stats(groups)
+                    frame = np.array(self.farfield, copy=True) if raw else None
+                bodies(1)
+                self._populate_pending = True            # a callback that reads farfield / amp_ff gets those of the new phase
+                if bar is not None:
+                    bar.update(1)
+                if callback is not None and callback(self):
+                    break                                # (:1727-1729: before the history entry and the counter)
+                # the slot of this iteration is written once: its flags (loss_result: the loss this body evaluated) and
+                # the statistics taken above
+                self._update_stats_batch(1, [self.flags.get("fixed_phase")], [stats], list(stats))
+                if frame is not None:
+                    _history_put(self.stats.setdefault("raw_farfield", []), self.iter, [frame])
+                self.iter += 1
+        if bar is not None:
+            bar.close()
+        # _populate_results (:1740), run when somebody asks (see optimize_gs)
         self._populate_pending = True
 
     def _flush_populate(self):
@@ -1393,6 +1511,11 @@ class SpotHologram(FeedbackHologram):
         self._calculate_stats_computational_spot(stats, stat_groups)
         self._update_stats_dictionary(stats)
 
+    def _calculate_stats(self, stat_groups):
+        stats = super()._calculate_stats(stat_groups)
+        self._calculate_stats_computational_spot(stats, stat_groups)
+        return stats
+
 
 __all__ = ["Hologram", "FeedbackHologram", "SpotHologram", "ALGORITHM_DEFAULTS", "ALGORITHM_INDEX",
            "FEEDBACK_OPTIONS"]
@@ -1617,6 +1740,10 @@ class CompressedSpotHologram(FeedbackHologram):
     def get_farfield(self, *args, **kwargs):
         raise NotImplementedError("CompressedSpotHologram has no DFT-grid farfield; see .farfield for the spots")
 
+    def optimize_cg(self, iterations, callback):
+        raise NotImplementedError("method 'CG' runs on the padded DFT grid (Hologram, SpotHologram); "
+                                  "CompressedSpotHologram is optimised with the GS / WGS methods")
+
 
 class MultiplaneHologram(Hologram):
     """
@@ -1722,6 +1849,10 @@ class MultiplaneHologram(Hologram):
 
     def get_farfield(self, *args, **kwargs):
         raise NotImplementedError("MultiplaneHologram has no farfield of its own; ask a child hologram")
+
+    def optimize_cg(self, iterations, callback):
+        raise NotImplementedError("method 'CG' optimises one hologram (Hologram, SpotHologram); "
+                                  "MultiplaneHologram is optimised with the GS / WGS methods")
 
     def optimize_gs(self, iterations, callback):
         """The loop of optimize_gs (:1465-1490) with the overloads of _multiplane.py:245-289."""

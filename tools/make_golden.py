@@ -729,6 +729,59 @@ def gen_compressed_cases(alg):
         save(f"compressed_{tag}", meta, rec)
 
 
+CG_CASES = {
+    # name: (padded shape, SLM shape, propagation kernel, array amplitude, dtypes)
+    "A": ((64, 64), (32, 48), True, False, (np.float64, np.float32)),
+    "B": ((128, 256), (100, 120), False, True, (np.float64,)),
+    "C": ((96, 80), (48, 40), False, False, (np.float64,)),       # no power of two: the general (Bluestein) transforms
+}
+CG_ITERS = 30
+
+
+def gen_cg_cases(alg):
+    """
+    optimize("CG") with the reference's defaults (ComplexMSELoss, torch Adam, lr 0.1) on the CPU.  Every input is drawn
+    in float32 and widened, so the float32 and float64 runs of one case start from the same numbers.  Recorded: the
+    inputs, the gradient autograd hands Adam in the first iteration, the loss of every iteration, the phase after 1, 2
+    and 5 steps.
+    """
+    for ci, (case, (shape, slm, with_kernel, with_amp, dtypes)) in enumerate(CG_CASES.items()):
+        seed = 700 + ci
+        target32 = synth.random_target(seed, shape, dtype=np.float32)
+        phase32 = synth.seed_phase(seed, slm, dtype=np.float32)
+        amp32 = synth.gaussian_amp(slm, dtype=np.float32) if with_amp else None
+        kernel32 = (0.3 * synth.seed_phase(seed + 50, slm)).astype(np.float32) if with_kernel else None
+        for dt in dtypes:
+            # (the reference's torch branch needs an amplitude ARRAY, _hologram.py:1014: a uniform beam is handed over as
+            #  ones, which the constructor normalises to the scalar 1 / sqrt(S) the tests construct with amp=None)
+            h = alg.Hologram(target32.astype(dt), amp=np.ones(slm, dtype=dt) if amp32 is None else amp32.astype(dt),
+                             phase=phase32.astype(dt), slm_shape=slm, dtype=dt,
+                             propagation_kernel=None if kernel32 is None else kernel32.astype(dt))
+            out = {"target": target32, "phase0": phase32, "start_phase": np.array(h.phase, copy=True)}
+            if amp32 is not None:
+                out["amp"] = amp32
+            if kernel32 is not None:
+                out["kernel"] = kernel32
+            loss = []
+
+            def snap(hh):
+                k = hh.iter + 1                     # steps taken so far (the callback runs before the counter moves)
+                loss.append(hh.flags["loss_result"])
+                if k == 1:
+                    out["grad_1"] = hh.optimizer.param_groups[0]["params"][0].grad.detach().numpy().copy()
+                if k in (1, 2, 5):
+                    out[f"phase_{k}"] = np.array(hh.phase, copy=True)
+                return False
+
+            h.optimize("CG", maxiter=CG_ITERS, verbose=False, callback=snap)
+            out["loss"] = np.array(loss, dtype=np.float64)
+            assert out["grad_1"].dtype == dt and out["phase_5"].dtype == dt and len(loss) == CG_ITERS
+            meta = dict(kind="cg", case=case, seed=seed, shape=shape, slm_shape=slm, dtype=np.dtype(dt).name,
+                        maxiter=CG_ITERS, optimizer="Adam", optimizer_kwargs={"lr": 0.1},
+                        amp="gaussian" if with_amp else "uniform", kernel_seed=seed + 50 if with_kernel else None)
+            save(f"cg_{case}_{'f32' if dt is np.float32 else 'f64'}", meta, out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg2", action="store_true")
@@ -749,6 +802,7 @@ def main():
         "kimeff": lambda: gen_kimeff_cases(alg),
         "spotnull": lambda: gen_spot_null_cases(alg),
         "feedback_ij": lambda: gen_feedback_ij_cases(alg),
+        "cg": lambda: gen_cg_cases(alg),
     }
     if args.cfg2:
         steps["cfg2"] = lambda: gen_cfg2(alg)
