@@ -59,6 +59,13 @@ def np_loss_and_gradient(phase, amp, kernel, target):
     return float(np.mean(r * r)), np.imag(np.conj(n[i0:i1, i2:i3]) * g)
 
 
+def adam_step(phase, m, v, g, t, lr=LR, betas=(BETA1, BETA2), eps=EPS):
+    """Step ``t`` (from 1) of torch.optim.Adam's update rule: returns the new (phase, m, v)."""
+    m = betas[0] * m + (1 - betas[0]) * g
+    v = betas[1] * v + (1 - betas[1]) * g * g
+    return phase - (lr / (1 - betas[0] ** t)) * m / (np.sqrt(v) / np.sqrt(1 - betas[1] ** t) + eps), m, v
+
+
 @functools.lru_cache(maxsize=None)
 def restatement(case):
     """(first gradient, {k: phase after k steps}, loss history) of the float64 restatement over the fixture's iterations."""
@@ -72,9 +79,7 @@ def restatement(case):
         loss, g = np_loss_and_gradient(phase, amp, h.propagation_kernel, target)
         losses.append(loss)
         grad1 = g if t == 1 else grad1
-        m = BETA1 * m + (1 - BETA1) * g
-        v = BETA2 * v + (1 - BETA2) * g * g
-        phase = phase - (LR / (1 - BETA1 ** t)) * m / (np.sqrt(v) / np.sqrt(1 - BETA2 ** t) + EPS)
+        phase, m, v = adam_step(phase, m, v, g, t)
         if t in STEPS:
             phases[t] = phase.copy()
     return grad1, phases, np.array(losses)
