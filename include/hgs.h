@@ -120,8 +120,10 @@ enum {
     HGS_SPOT_COEFF = 16,  /* real [n_monomials][n_spots]       ... and weights (phase.py:850-920)    */
     HGS_PHASE_PREV = 17,  /* get only: [batch][slm_h][slm_w] real -- the phase the last one-iteration hgs_iterate call
                              STARTED from (HGS_OPT_KEEP_PREV_PHASE); HGS_ERR_STATE when none is held */
-    HGS_CG_GRAD = 18      /* get only: [slm_h][slm_w] real -- dL/dphase of the last hgs_cg_iterate body that kept it
+    HGS_CG_GRAD = 18,     /* get only: [slm_h][slm_w] real -- dL/dphase of the last hgs_cg_iterate body that kept it
                              (hgs_cg_params.keep_grad); HGS_ERR_STATE before the first such body */
+    HGS_VORTICES = 19     /* get only: int32 [n][3] (x, y, winding) -- the vortices the last hgs_remove_vortices call found and
+                             removed, n its n_removed; HGS_ERR_STATE before the first call */
 };
 
 int hgs_create(const hgs_config* cfg, hgs_engine** out);
@@ -205,6 +207,20 @@ typedef struct {
  * (HGS_ERR_UNSUPPORTED otherwise); power-of-two and general padded shapes alike. */
 int hgs_cg_iterate(hgs_engine* e, const hgs_cg_params* params, int n_iter, double* loss_out);
 
+/* Hologram._remove_vortices (_hologram.py:961-998) as its code intends -- the reference acts only under plot=True --:
+ * analysis.image_remove_vortices(phase_ff, target > 0) (analysis/__init__.py:1207-1309) on the stored HGS_PHASE_FF.
+ *   winding(y, x) = rint(-(dd0[y, x] - dd1[y, x] - dd0[y, x - 1] + dd1[y - 1, x]) / 2 pi),  dd_a = mod(diff_a(phase) - pi, 2 pi):
+ *       the winding of the plaquette (y-1..y, x-1..x); row 0 and column 0 hold none;
+ *   a vortex counts where the whole 5 x 5 neighbourhood of (y, x) lies inside the grid with target > 0 (binary_erosion with a
+ *       zero border; NaN pixels of an MRAF target are outside);
+ *   phase_ff -= sum over those vortices of  w * atan2(X - x, Y - y),  X, Y the pixel indices (the reference's argument
+ *       order, x first), over the WHOLE image and without wrapping.
+ * The list is built in a fixed order (count, scan, scatter), so two calls on the same state agree to the bit in either
+ * precision.  n_removed (optional) receives the number of vortices; hgs_get_array(HGS_VORTICES) returns them.  The
+ * farfield, amp_ff, the weights, the phase and the statistics are untouched.  kind 0 and batch 1 only (HGS_ERR_UNSUPPORTED
+ * otherwise); HGS_ERR_STATE when no phase_ff is held or no target is set; power-of-two and general padded shapes alike. */
+int hgs_remove_vortices(hgs_engine* e, int32_t* n_removed);
+
 /* MultiplaneHologram._farfield2nearfield (_multiplane.py:255-279): every child runs
  * _farfield2nearfield(extract=False) on its own (constrained) farfield; the children's complex
  * nearfields over the SLM are summed on the device,
@@ -283,7 +299,8 @@ int hgs_iterate_timed(hgs_engine* e, hgs_step* step, int n_iter, double* ms);
  *     "col_tile_kernel<R=float,N=4096,PHASE=0,NR=6,STATS=false,EXTRAS=false,RULE=1,LISTED=0> xmap\t50\n"
  * (family, its template arguments by name -- the ones rocprofv3 prints positionally --, flags list / load_mask /
  * store_mask / xmap / batch / stats / nf_out, launch count).  Families: row_kernel, col_kernel, col_fused_kernel,
- * col_tile_kernel, bluestein_lines, c_n2f_run, c_f2n_run, c_n2f_partial, c_f2n, cgemm_streamk, cg_seed_kernel, cg_adam_kernel
+ * col_tile_kernel, bluestein_lines, c_n2f_run, c_f2n_run, c_n2f_partial, c_f2n, cgemm_streamk, cg_seed_kernel, cg_adam_kernel,
+ * vortex_find_kernel, vortex_remove_kernel
  * (the small element-wise / reduction helpers are not recorded).  The tests assert it next to the numbers: neighbouring variants often agree to
  * the last bit, so only this shows that a policy reached the kernel it names.  `needed` (optional) receives the bytes
  * the text takes including the terminator; with buf = NULL and nbytes = 0 the call is a size query and keeps the record,

@@ -22,6 +22,7 @@ OPT_KEEP_PREV_PHASE = 8
  SPOT_AMP, EXTERNAL_AMP, ZERO_WEIGHTS, XGRID, YGRID, MONOMIALS, SPOT_COEFF) = range(17)
 PHASE_PREV = 17
 CG_GRAD = 18
+VORTICES = 19
 FB_PIXEL, FB_SPOT_WINDOW, FB_EXTERNAL = 0, 1, 2
 K_NAMES = ("row", "col_fused", "col_fwd", "col_inv", "elementwise", "cg_seed", "cg_adam")
 
@@ -109,6 +110,7 @@ def load():
         "hgs_iterate_stats": (C.c_int, [eng, P(hgs_step), C.c_int, P(C.c_uint8), C.c_int, C.c_int,
                                         P(C.c_double), P(C.c_double)]),
         "hgs_cg_iterate": (C.c_int, [eng, P(hgs_cg_params), C.c_int, P(C.c_double)]),
+        "hgs_remove_vortices": (C.c_int, [eng, P(C.c_int32)]),
         "hgs_sync": (C.c_int, [eng]),
         "hgs_set_option": (C.c_int, [eng, C.c_int, C.c_int]),
         "hgs_profile_enable": (C.c_int, [eng, C.c_int]),
@@ -128,7 +130,7 @@ def load():
 
 EXPORTS = ("hgs_create", "hgs_destroy", "hgs_set_array", "hgs_get_array", "hgs_get_array_device", "hgs_set_array_device", "hgs_copy_phase",
            "hgs_reset_weights", "hgs_reset", "hgs_set_array_sparse", "hgs_nearfield2farfield", "hgs_farfield_constraint",
-           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_cg_iterate", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
+           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_cg_iterate", "hgs_remove_vortices", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
            "hgs_profile_read", "hgs_iterate_timed", "hgs_dispatch_read", "hgs_last_error", "hgs_version")
 
 

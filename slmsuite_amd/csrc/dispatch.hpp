@@ -67,6 +67,8 @@ HGS_FAMILY(KCf2nPix, "c_f2n", "R,DEG");
 HGS_FAMILY(KCgemm, "cgemm_streamk", "R,EPI");
 HGS_FAMILY(KCgSeed, "cg_seed_kernel", "R");
 HGS_FAMILY(KCgAdam, "cg_adam_kernel", "R");
+HGS_FAMILY(KVortexFind, "vortex_find_kernel", "R");
+HGS_FAMILY(KVortexRemove, "vortex_remove_kernel", "R");
 #undef HGS_FAMILY
 
 }  // namespace hgs

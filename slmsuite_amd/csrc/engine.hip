@@ -20,6 +20,7 @@
 #include "compressed_sep.hpp"
 #include "bluestein.hpp"
 #include "cg_kernels.hpp"
+#include "vortex_kernels.hpp"
 #include <complex>
 #include <dlfcn.h>
 
@@ -163,6 +164,7 @@ struct EngineBase {
     virtual int profile_read(double* out) = 0;
     virtual int iterate_timed(hgs_step* st, int n, double* ms) = 0;
     virtual int cg_iterate(const hgs_cg_params* p, int n, double* loss_out) = 0;
+    virtual int remove_vortices(int32_t* n_removed) = 0;
 };
 
 template <typename R> struct Engine : EngineBase {
@@ -240,6 +242,13 @@ template <typename R> struct Engine : EngineBase {
     double* cg_loss = nullptr;         // [cg_loss_cap] sum r^2 of each body
     int cg_loss_cap = 0, cg_t = 0;
     bool cg_have_grad = false;
+    // hgs_remove_vortices: per-block counts / offsets of the search, the list (x, y, w) of the last call (grown to the
+    // count the host reads once per call) and that count, device resident for the removal; vx_n: the host's copy, -1 = no call yet
+    unsigned* vx_counts = nullptr;
+    int32_t* vx_list = nullptr;
+    int32_t* vx_count = nullptr;
+    unsigned vx_cap = 0;
+    int vx_n = -1;
     // per-column kernel (float64; float32 where the tile-resident kernel does not run) single-pass MRAF: noise part as farfield
     // values, the columns that hold it, their inverse pass
     C* ffb = nullptr;                      // [B][P], layout of ff; only NaN-target pixels are ever written, the rest stays zero
@@ -326,7 +335,7 @@ template <typename R> struct Engine : EngineBase {
     ~Engine() override {
         if (stream) hipStreamSynchronize(stream);
         if (tw_col == tw_row) tw_col = nullptr;
-        void* ptrs[] = {cg_m, cg_v, cg_grad, cg_partial, cg_loss, phase_prev, ffb, col_list_signal, n_signal_dev, col_list_noise, n_noise_dev, lane_mask_tmp, lane_mask_noise, phase, amp, kern, gh, gh2, w, t, pff, ff, aff, zw, staging, tw_row, tw_col, wpartial, dpartial,
+        void* ptrs[] = {vx_counts, vx_list, vx_count, cg_m, cg_v, cg_grad, cg_partial, cg_loss, phase_prev, ffb, col_list_signal, n_signal_dev, col_list_noise, n_noise_dev, lane_mask_tmp, lane_mask_noise, phase, amp, kern, gh, gh2, w, t, pff, ff, aff, zw, staging, tw_row, tw_col, wpartial, dpartial,
                         fpartial, epartial, sums, wscale, spot_xy, spot_amp, ext_amp, spot_fb, nfbuf, nog_dev, stats_scratch, stats_dxy, col_active, sig_rows, col_list, n_active_dev, lane_mask, col_active_d, col_list_d, n_active_d_dev, lane_mask_d, stat_partial, stat_tsum, xg, yg, mono, coeff, cpartial, cnorm, ext_r, sep_c, sep_g, sep_ex, sep_exT, sep_ey, sep_nfT, sep_b2, sep_c1, sep_c2, sep_norm, run_rec, run_ys, run_nf, sk_tab};
         for (void* p : ptrs)
             if (p) hipFree(p);
@@ -1370,6 +1379,14 @@ template <typename R> struct Engine : EngineBase {
                 HIPCHK(hipStreamSynchronize(stream));
                 return 0;
             }
+            case HGS_VORTICES: {
+                if (vx_n < 0) return fail(HGS_ERR_STATE, "no vortex list is held (hgs_remove_vortices has not run)");
+                if (nbytes != (size_t)vx_n * 3 * sizeof(int32_t)) return fail(HGS_ERR_ARG, "vortices: bad size %zu (the last call found %d)", nbytes, vx_n);
+                if (vx_n == 0) return 0;
+                HIPCHK(hipMemcpyAsync(dst, vx_list, nbytes, dst_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                return 0;
+            }
             case HGS_TARGET: return download_T<R>(t, dst, nbytes, dst_device, nullptr);
             case HGS_WEIGHTS: return download_T<R>(w, dst, nbytes, dst_device, w_pending ? wscale : nullptr);
             case HGS_PHASE_FF:
@@ -1806,6 +1823,54 @@ template <typename R> struct Engine : EngineBase {
             HIPCHK(hipStreamSynchronize(stream));
             for (int it = 0; it < n; ++it) loss_out[it] /= (double)P;      // mean reduction
         }
+        return 0;
+    }
+
+    // Hologram._remove_vortices (:961-998) as its code intends: analysis.image_remove_vortices(phase_ff, target > 0) on the
+    // stored farfield phase (vortex_kernels.hpp).  Search pass 0 counts, the scan leaves offsets and the total on the
+    // device, the host reads the total once (it sizes the list and is the return value), pass 1 scatters, the removal
+    // walks the list.  Nothing else of the engine's state is touched.
+    int remove_vortices(int32_t* n_removed) override {
+        RoctxRange range(opt_roctx, "hgs_remove_vortices");
+        if (cfg.kind != 0) return fail(HGS_ERR_UNSUPPORTED, "hgs_remove_vortices: padded-grid holograms only (engine kind 0)");
+        if (B != 1) return fail(HGS_ERR_UNSUPPORTED, "hgs_remove_vortices: one hologram per engine (batch is %d)", B);
+        if (!pff || !have_pff) return fail(HGS_ERR_STATE, "phase_ff has not been computed");
+        if (!has_target) return fail(HGS_ERR_STATE, "target has not been set");
+        const unsigned blocks = vortex_find_blocks(P);
+        if (!vx_counts) { if (dalloc(&vx_counts, (size_t)blocks)) return HGS_ERR_DEVICE; }
+        if (!vx_count) { if (dalloc(&vx_count, (size_t)1)) return HGS_ERR_DEVICE; }
+        vx_n = -1;
+        VortexFindArgs<R> f{};
+        f.pff = pff; f.t = t; f.counts = vx_counts; f.list = vx_list; f.cap = vx_cap; f.pass = 0; f.P = P;
+        f.g = VxGeo{g.Ph, g.Pw, g.lane_T};
+        int n = 0;
+        int r = timed(HGS_K_ELEMENTWISE, [&]() -> int {
+            LCHK(launch_vortex_find<R>(stream, f));
+            LCHK(launch_vortex_scan(stream, vx_counts, blocks, vx_count));
+            return 0;
+        });
+        if (r) return r;
+        HIPCHK(hipMemcpyAsync(&n, vx_count, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (n > 0) {
+            if ((unsigned)n > vx_cap) {
+                if (vx_list) { HIPCHK(hipFree(vx_list)); vx_list = nullptr; vx_cap = 0; }
+                const size_t cap = std::max<size_t>(1024, (size_t)n + (size_t)n / 2);      // (a cleaned phase holds fewer the next time)
+                if (dalloc(&vx_list, 3 * cap)) return HGS_ERR_DEVICE;
+                vx_cap = (unsigned)cap;
+            }
+            r = timed(HGS_K_ELEMENTWISE, [&]() -> int {
+                f.list = vx_list; f.cap = vx_cap; f.pass = 1;
+                LCHK(launch_vortex_find<R>(stream, f));
+                VortexRemoveArgs<R> a{};
+                a.pff = pff; a.list = vx_list; a.count = vx_count; a.P = P; a.g = f.g;
+                LCHK(launch_vortex_remove<R>(stream, a));
+                return 0;
+            });
+            if (r) return r;
+        }
+        vx_n = n;
+        if (n_removed) *n_removed = n;
         return 0;
     }
 
@@ -2670,6 +2735,7 @@ int hgs_cg_iterate(hgs_engine* e, const hgs_cg_params* params, int n_iter, doubl
     if (!params) return hgs::fail(HGS_ERR_ARG, "null parameters");
     return e->impl->cg_iterate(params, n_iter, loss_out);
 }
+int hgs_remove_vortices(hgs_engine* e, int32_t* n_removed) { ENG(e) return e->impl->remove_vortices(n_removed); }
 int hgs_iterate_stats(hgs_engine* e, hgs_step* step, int n_iter, uint8_t* hist, int stat_groups, int width,
                       const double* spot_xy_float, double* stats_out) {
     ENG(e)

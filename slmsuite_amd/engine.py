@@ -207,6 +207,25 @@ class Engine:
         L.check(self.lib.hgs_get_array(self._h, L.CG_GRAD, out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
 
+    def remove_vortices(self):
+        """
+        hgs_remove_vortices: subtract the phase vortices inside the eroded ``target > 0`` mask from the stored
+        HGS_PHASE_FF, on the device.  Returns how many were removed.
+        """
+        n = C.c_int32(0)
+        L.check(self.lib.hgs_remove_vortices(self._h, C.byref(n)))
+        self._n_vortices = int(n.value)
+        return self._n_vortices
+
+    def get_vortices(self):
+        """HGS_VORTICES: int32 ``[n, 3]`` (x, y, winding) of the last ``remove_vortices()``, in the engine's list order."""
+        n = getattr(self, "_n_vortices", None)
+        if n is None:
+            raise L.HgsError("no vortex list is held (remove_vortices has not run)")
+        out = np.empty((max(n, 1), 3), dtype=np.int32)[:n]
+        L.check(self.lib.hgs_get_array(self._h, L.VORTICES, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
     def iterate_timed(self, step, n_iter):
         ms = C.c_double()
         L.check(self.lib.hgs_iterate_timed(self._h, C.byref(step), int(n_iter), C.byref(ms)))

@@ -279,6 +279,7 @@ class Hologram:
         self._stale -= {"amp_ff", "phase_ff", "farfield"}
         self._upload.discard("phase_ff")
         self._populate_pending = False
+        self._pff_cleaned = False
         if self._engine is not None:
             # weights from its target, phase_ff / farfield / amp_ff back to "None" (hgs_reset); a phase only the device
             # holds (reset_phase False after an optimize()) simply stays there
@@ -799,7 +800,8 @@ class Hologram:
             state["pff"] = True
             if "phase_ff" in self._upload:                     # assigned by this callback: that is what it reads back
                 return
-            prev = e.get_prev_phase() if state["bodies"] > 0 else None
+            # (a phase_ff cleaned by remove_vortices() and still fixed: the engine's copy is the one that counts, below)
+            prev = e.get_prev_phase() if state["bodies"] > 0 and not self.__dict__.get("_pff_cleaned") else None
             if prev is not None:
                 side = self._side_engine(self.shape)
                 side.set(L.PHASE, prev)
@@ -903,6 +905,8 @@ class Hologram:
                         self._stale.add("phase")
                     e = self._get_engine()
                     st = self._make_step(efficiency_group=eg)
+                    if not self.flags.get("fixed_phase", False):
+                        self._pff_cleaned = False            # this body describes (or stores) a farfield phase of its own
                     if groups:
                         hist, per_iter = e.iterate_stats(st, 1, groups, width, xy)
                     else:
@@ -1104,6 +1108,78 @@ class Hologram:
         e = self._get_engine()
         e.nearfield2farfield(store_phase_ff=True)
         self._mark_device_fresh(["farfield", "amp_ff", "phase_ff"])
+        self._pff_cleaned = False
+
+    # ---- phase-vortex removal (_hologram.py:961-998, analysis/__init__.py:1207-1309) ---------------------------------------
+    def remove_vortices(self):
+        """
+        Remove the phase vortices of the stored farfield phase where the target is positive -- what the reference's
+        ``_remove_vortices`` is written to do (it acts only under ``plot=True``): ``analysis.image_remove_vortices(phase_ff,
+        target > 0)``, on the engine (hgs_remove_vortices).  ``phase_ff`` stays on the device; a host copy is made only
+        when somebody reads it.  Meant for a ``callback=`` of ``optimize()``; it matters to the loop while the phase is
+        fixed (WGS-Kim), as in the reference.  Returns the number of vortices removed, 0 when there is no ``phase_ff``.
+        """
+        state = self.__dict__.get("_midloop")
+        if state is None:
+            return self._remove_vortices_now(None)
+        # inside a callback of the device-resident loop: a phase the callback assigned is held back, as for the reads
+        # (_midloop_materialise)
+        held = "phase" in self._upload
+        self._upload.discard("phase")
+        try:
+            return self._remove_vortices_now(state)
+        finally:
+            if held:
+                self._upload.add("phase")
+
+    def _remove_vortices_now(self, state):
+        if self.__dict__.get("_populate_pending"):
+            self._flush_populate()                   # the previous call's trailing transform: phase_ff of its final phase
+            if state is not None:
+                state["ff"] = state["pff"] = True
+        elif (state is not None and state["bodies"] > 0 and not state.get("pff") and "phase_ff" not in self._upload
+              and self._engine is not None):
+            if self.flags.get("fixed_phase", False) or self.__dict__.get("_pff_cleaned"):
+                self._stale.add("phase_ff")          # a fixed phase: the engine's HGS_PHASE_FF is the array itself
+                self._upload.discard("phase_ff")
+            else:
+                # the fused bodies do not store the farfield phase while it is free (and the next body will not read it):
+                # form it as a read would, then clean that
+                self._midloop_materialise_held("phase_ff", state)
+                if self._host.get("phase_ff") is not None and "phase_ff" not in self._stale:
+                    self._upload.add("phase_ff")
+        elif (state is not None and state.get("pff") and self._host.get("phase_ff") is not None
+              and "phase_ff" not in self._stale):
+            self._upload.add("phase_ff")             # the callback has read it already: what it saw is what is cleaned
+        if self._host.get("phase_ff") is None and "phase_ff" not in self._stale:
+            return 0
+        e = self._get_engine()                       # pushes a phase_ff the caller edited on the host
+        n = e.remove_vortices()
+        self._mark_device_fresh(["phase_ff"])
+        if state is not None:
+            state["pff"] = True
+            self._pff_cleaned = True
+        return n
+
+    def _remove_vortices(self, plot=False):
+        """The reference's name of ``remove_vortices()``; its debug plots are not part of this build."""
+        if plot:
+            raise NotImplementedError("remove_vortices: plotting is outside this build")
+        return self.remove_vortices()
+
+    def get_vortices(self):
+        """
+        ``((rows, cols), weights)`` of the vortices the last ``remove_vortices()`` removed, in row-major order like
+        ``analysis.image_vortices_coordinates``; empty before the first call.
+        """
+        n = getattr(self._engine, "_n_vortices", None) if self._engine is not None else None
+        if not n:
+            z = np.zeros(0, dtype=np.intp)
+            return (z, z.copy()), np.zeros(0, dtype=self.dtype)
+        v = self._engine.get_vortices()
+        order = np.lexsort((v[:, 0], v[:, 1]))
+        v = v[order]
+        return (v[:, 1].astype(np.intp), v[:, 0].astype(np.intp)), v[:, 2].astype(self.dtype)
 
     # mempool helpers of the reference have no meaning here
     @staticmethod
@@ -1371,6 +1447,10 @@ class SpotHologram(FeedbackHologram):
     def __len__(self):
         return self.spot_knm.shape[1]
 
+    def remove_vortices(self):
+        """Spot holograms do not need to consider vortices (_spots.py:16)."""
+        return 0
+
     def _n_spots(self):
         return self.spot_knm.shape[1]
 
@@ -1621,6 +1701,10 @@ class CompressedSpotHologram(FeedbackHologram):
     def __len__(self):
         return self.spot_amp.size
 
+    def remove_vortices(self):
+        """Spot holograms do not need to consider vortices (_spots.py:16)."""
+        return 0
+
     def _n_spots(self):
         return len(self)
 
@@ -1794,6 +1878,10 @@ class MultiplaneHologram(Hologram):
         return len(self.holograms)
 
     # ---- the shared phase ---------------------------------------------------------------------------
+    def remove_vortices(self):
+        """_multiplane.py:288: every child removes its own; returns the total."""
+        return sum(int(h.remove_vortices() or 0) for h in self.holograms)
+
     def _get_dev(self, name):
         if name == "phase" and "phase" in self._stale:
             self._host["phase"] = self.holograms[0].phase

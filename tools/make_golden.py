@@ -782,6 +782,128 @@ def gen_cg_cases(alg):
             save(f"cg_{case}_{'f32' if dt is np.float32 else 'f64'}", meta, out)
 
 
+def _disc(shape, radius_frac=0.3, dtype=np.float32):
+    h, w = shape
+    y, x = np.mgrid[0:h, 0:w]
+    return (((y - h / 2) ** 2 + (x - w / 2) ** 2) <= (radius_frac * min(h, w)) ** 2).astype(dtype)
+
+
+def _vortex_reference(analysis, phase32, target32, dt):
+    """The three analysis functions on one input in precision ``dt``: winding image, masked list, cleaned phase."""
+    from scipy.ndimage import binary_erosion
+    p = phase32.astype(dt)
+    mask = target32 > 0
+    wind = analysis.image_vortices(p.copy())
+    coords, weights = analysis.image_vortices_coordinates(p.copy(), mask=binary_erosion(mask, np.ones((5, 5))))
+    cleaned = analysis.image_remove_vortices(p.copy(), mask)
+    assert cleaned.dtype == dt
+    rc, rw = analysis.image_vortices_coordinates(cleaned.copy(), mask=binary_erosion(mask, np.ones((5, 5))))
+    return dict(wind=wind, rows=coords[0], cols=coords[1], weights=weights, cleaned=cleaned,
+                res_rows=rc[0], res_cols=rc[1], res_weights=rw)
+
+
+VORTEX_D_SHAPE = (56, 72)
+VORTEX_D_HOLE = (slice(24, 34), slice(30, 44))       # target == 0 here: the eroded mask ends two pixels around it
+# (y, x, sign) of the planted plaquettes -- the winding image entry -- and whether the eroded mask holds them
+VORTEX_D_PLANTED = [
+    (1, 1, +1, False), (55, 20, -1, False), (30, 71, +1, False), (0, 40, -1, False), (20, 0, +1, False),   # borders
+    (2, 2, -1, True), (53, 69, +1, True),                                            # first / last pixel the erosion keeps
+    (21, 33, +1, True), (22, 40, -1, False),                                         # above the hole: row 21 inside, row 22 eroded
+    (26, 27, -1, True), (31, 28, +1, False),                                         # left of it: column 27 inside, 28 eroded
+    # (no two on neighbouring plaquettes: the phase step across a shared edge would sit at the wrap boundary)
+    (40, 50, +1, True), (12, 60, -1, True), (45, 12, -1, True),
+]
+
+
+def gen_vortex_cases(alg, analysis):
+    """
+    analysis.image_vortices / image_vortices_coordinates / image_remove_vortices (analysis/__init__.py:1207-1309) on stored
+    farfield phases, recorded in float64 and float32 from the same float32-drawn inputs.  A - D: one removal each (inputs,
+    winding image, list, cleaned phase, and the list the reference finds on its own output); E: a float64 WGS-Kim run whose
+    callback removes the vortices of the fixed phase once.  Refuses to save a case whose float32 and float64 lists differ.
+    """
+    cases = {}
+    # A: a real stored phase -- phase_ff of a short WGS-Kim run on a disc target
+    shape, slm = (64, 64), (32, 32)
+    target = _disc(shape)
+    h = alg.Hologram(target.copy(), phase=synth.seed_phase(811, slm), slm_shape=slm, dtype=np.float32)
+    h.optimize("WGS-Kim", maxiter=6, verbose=False, fix_phase_iteration=2)
+    cases["A"] = (shape, slm, target, np.array(h.phase_ff, dtype=np.float32), dict(seed=811))
+    # B: neither square nor a power of two
+    shape, slm = (48, 80), (24, 40)
+    cases["B"] = (shape, slm, 0.1 + synth.random_target(812, shape), synth.seed_phase(813, shape), dict(seed=812))
+    # C: dense target, uniform random phase: thousands of vortices
+    shape, slm = (128, 128), (64, 64)
+    cases["C"] = (shape, slm, 0.1 + synth.random_target(814, shape), synth.seed_phase(815, shape), dict(seed=814))
+    # D: planted vortices (half-pixel centres: entry (y, x) of the winding image is the plaquette (y-1..y, x-1..x))
+    shape, slm = VORTEX_D_SHAPE, (28, 36)
+    target = np.ones(shape, dtype=np.float32)
+    target[VORTEX_D_HOLE] = 0
+    yy, xx = np.mgrid[0:shape[0], 0:shape[1]].astype(np.float64)
+    phase = np.zeros(shape)
+    for (y, x, sgn, _) in VORTEX_D_PLANTED:
+        phase += sgn * np.arctan2(yy - (y - 0.5), xx - (x - 0.5))
+    cases["D"] = (shape, slm, target, phase.astype(np.float32), dict(planted=[list(map(int, v[:3])) + [bool(v[3])] for v in VORTEX_D_PLANTED]))
+
+    for case, (shape, slm, target32, phase32, extra) in cases.items():
+        r64 = _vortex_reference(analysis, phase32, target32, np.float64)
+        r32 = _vortex_reference(analysis, phase32, target32, np.float32)
+        for k in ("wind", "rows", "cols", "weights", "res_rows", "res_cols", "res_weights"):
+            assert np.array_equal(r64[k], r32[k]), f"vortex {case}: float32 and float64 disagree on {k}: choose another seed"
+        n = len(r64["rows"])
+        if case == "C":
+            assert n > 1024, n
+        if case == "D":
+            # the reference's sign convention is whatever it is; the places are known exactly
+            want = sorted((y, x) for (y, x, _, inside) in VORTEX_D_PLANTED if inside)
+            assert sorted(zip(r64["rows"].tolist(), r64["cols"].tolist())) == want, (sorted(zip(r64["rows"], r64["cols"])), want)
+            seen = sorted(zip(*np.nonzero(r64["wind"])))
+            assert seen == sorted((y, x) for (y, x, _, _) in VORTEX_D_PLANTED if y > 0 and x > 0), seen
+        out = dict(target=target32, phase_ff=phase32, winding=r64["wind"].astype(np.int8),
+                   rows=r64["rows"].astype(np.int32), cols=r64["cols"].astype(np.int32), weights=r64["weights"].astype(np.int32),
+                   cleaned_f64=r64["cleaned"], cleaned_f32=r32["cleaned"],
+                   res_rows=r64["res_rows"].astype(np.int32), res_cols=r64["res_cols"].astype(np.int32),
+                   res_weights=r64["res_weights"].astype(np.int32))
+        meta = dict(kind="vortex", case=case, shape=shape, slm_shape=slm, n=n, n_residual=len(r64["res_rows"]), **extra)
+        print(f"  vortex {case}: K = {n}, residual {len(r64['res_rows'])}")
+        save(f"vortex_{case}", meta, out)
+
+    # E: WGS-Kim, float64, the phase fixed early; the callback cleans the fixed phase_ff once.  Pixel-wise WGS amplifies
+    # rounding from body to body, so geometry and length are chosen by the reference's OWN sensitivity: the run is
+    # repeated from a seed phase moved by one ulp, and the case is refused unless the two ends agree to 1e-10 -- a factor
+    # of ten under the 1e-9 a float64 WGS-Kim run is held to (a 32 x 32 SLM in a 64 x 64 pad, 12 bodies: 9e-8; this one: 1e-12)
+    shape, slm, n_iter, fix_at, clean_at = (64, 64), (64, 64), 10, 3, 5
+    target32, phase32 = _disc(shape), synth.seed_phase(821, slm)
+    finals = {}
+    for clean in (True, False, "moved"):
+        phase0 = phase32.astype(np.float64)
+        if clean == "moved":
+            phase0 = np.nextafter(phase0, np.inf)
+        h = alg.Hologram(target32.astype(np.float64), phase=phase0, slm_shape=slm, dtype=np.float64)
+        removed = []
+
+        def cb(hh):
+            if clean and hh.iter == clean_at:
+                assert hh.flags["fixed_phase"]
+                before = np.array(hh.phase_ff, copy=True)
+                analysis.image_remove_vortices(hh.phase_ff, hh.target > 0)
+                removed.append(float(np.abs(hh.phase_ff - before).max()))
+            return False
+
+        h.optimize("WGS-Kim", maxiter=n_iter, verbose=False, fix_phase_iteration=fix_at, callback=cb)
+        finals[clean] = (np.array(h.phase, copy=True), np.array(h.phase_ff, copy=True), removed)
+    assert finals[True][2] and finals[True][2][0] > 0, "case E: the callback removed nothing"
+    dist = lambda a, b: float(np.sqrt(np.mean(np.abs(np.exp(1j * a) - np.exp(1j * b)) ** 2)))
+    change = dist(finals[True][0], finals[False][0])
+    own = (dist(finals[True][0], finals["moved"][0]), dist(finals[True][1], finals["moved"][1]))
+    assert max(own) < 1e-10, f"case E: the reference itself moves by {own} under one ulp of the seed phase"
+    assert change > 1e-3, f"case E: the removal does not change the final phase ({change})"
+    print(f"  vortex E: final phase moved by {change:.3g} (phasor rms); one ulp of the seed moves phase / phase_ff by {own[0]:.2g} / {own[1]:.2g}")
+    meta = dict(kind="vortex", case="E", shape=shape, slm_shape=slm, dtype="float64", method="WGS-Kim", maxiter=n_iter,
+                fix_phase_iteration=fix_at, clean_at=clean_at, seed=821, change=change, own_sensitivity=list(own))
+    save("vortex_E", meta, dict(target=target32, phase0=phase32, final_phase=finals[True][0], final_phase_ff=finals[True][1]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg2", action="store_true")
@@ -803,6 +925,7 @@ def main():
         "spotnull": lambda: gen_spot_null_cases(alg),
         "feedback_ij": lambda: gen_feedback_ij_cases(alg),
         "cg": lambda: gen_cg_cases(alg),
+        "vortex": lambda: gen_vortex_cases(alg, analysis),
     }
     if args.cfg2:
         steps["cfg2"] = lambda: gen_cfg2(alg)
