@@ -38,6 +38,8 @@ struct Tuning {
     int mraf_presum = 1;        // HGS_MRAF_PRESUM=0: the two-inverse split form on every update
     int presum_rows = 1;        // HGS_PRESUM_ROWS=0
     int presum_blocks = 0;      // HGS_PRESUM_BLOCKS: workgroups of the pre-pass (0 = tuned)
+    int empty_col_loads = 1;    // HGS_EMPTY_COL_LOADS=0 / HGS_OPT_EMPTY_COL_LOADS: the half-width tile kernel fetches weights and targets of
+                                // every column, also of those the scan found empty (the tests' A/B reference)
     int sparse = 1;             // HGS_OPT_SPARSE_COLUMNS
     int tile = 1;               // HGS_OPT_TILE_KERNEL (0 forces the per-column kernel at every size: the tests' A/B reference)
 };
@@ -54,6 +56,8 @@ struct PassFacts {
     bool w_unit = false;            // the stored weights are normalised by wscale (Engine::w_unit)
     bool sparse_enabled = false;    // the column pass walks the list of active columns
     bool sparse_tiles = false, sparse_dirty = true;
+    bool w_outside_scan = false;    // a kernel that the scan does not see may have written a weight into a column it found empty
+                                    // (the N-vector rule of the spot feedback modes writes at the spot pixels, whatever the target holds)
     int n_active_min = 0, n_active_max = 0, n_noise_max = 0, n_signal_max = 0;
     bool ffb_unavailable = false;   // the device could not give the farfield buffer of the float64 split form
     Tuning tun;
@@ -276,6 +280,10 @@ inline ColLaunch column_launch(const PassFacts& f, const MrafForms& m, const Col
         l.rule = l.do_update ? 1 : 2;
         l.grid = t2;
         l.few_active = !f.sparse_dirty && f.n_active_min > 0 && f.n_active_max * 4 <= f.Pw;
+        // ... and the scan's column flags go with it: weights / targets are requested only in the columns that hold any
+        // (current scan only -- every writer of either array outside the column kernels marks it dirty or is named above)
+        // (4096 rows, at most five slots: the instances of col_tile2_kernel that read them, WTBUF)
+        l.col_flags = l.few_active && f.Ph == 4096 && l.nr <= 5 && t.empty_col_loads && !f.w_outside_scan;
         l.half_xmap = f.Ph >= 4096 && t2 % 16 == 0;
     } else if (m.tile_path) {
         l.grid = tile_grid;

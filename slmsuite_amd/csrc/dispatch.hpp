@@ -20,6 +20,7 @@ enum : unsigned {
     DF_BATCH = 16u,      // grid.y > 1
     DF_STATS = 32u,      // in-pass statistics requested (ColArgs::do_stats)
     DF_NF_OUT = 64u,     // complex nearfield kept (MultiplaneHologram)
+    DF_COL_FLAGS = 128u, // the column scan's flags go with the launch (ColArgs::col_flags)
 };
 
 struct DispatchSite {

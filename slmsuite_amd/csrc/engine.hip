@@ -83,7 +83,7 @@ thread_local DispatchLog* g_dispatch = nullptr;
 // one line per (kernel instance, run-time flags): "family<P0=v0,...> flag ...\tcount\n".  The argument values come from
 // __PRETTY_FUNCTION__ of dispatch_site<Fam, R, V...>: "... [Fam = hgs::KTile, R = float, V = <4096, 1, 6, false, false, 1, 0>]"
 std::string DispatchLog::text() const {
-    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out"};
+    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags"};
     std::string out;
     for (const Ent& e : v) {
         std::vector<std::string> vals;
@@ -217,6 +217,11 @@ template <typename R> struct Engine : EngineBase {
     bool dil_valid = false;
     int n_active_max = 0, n_active_min = 0;
     bool sparse_dirty = true;
+    // spot_update (the N-vector rule) has written weights at the spot pixels since the last column scan: a spot whose target
+    // and weight were zero then sits in a column the scan found empty, and a NaN factor turns its weight into 1e-4.  The column
+    // lists keep their meaning (such a pixel never had a target), the per-column load flags of col_tile2_kernel are withheld
+    // until the next scan, which the next dense call that could use them runs itself (iterate()).
+    bool w_outside_scan = false;
     bool sparse_tiles = false;             // the active set is whole 4-column tiles (the tile-resident kernel walks the list)
     // engine policy (hgs_set_option) and the developer switches, read from the environment once, in init() (read_tuning)
     Tuning tun;
@@ -409,6 +414,7 @@ template <typename R> struct Engine : EngineBase {
         t.mraf_presum = env_int("HGS_MRAF_PRESUM", 1);
         t.presum_rows = env_int("HGS_PRESUM_ROWS", 1);
         t.presum_blocks = env_int("HGS_PRESUM_BLOCKS", 0);
+        t.empty_col_loads = env_int("HGS_EMPTY_COL_LOADS", 1);
         return t;
     }
 
@@ -1352,6 +1358,7 @@ template <typename R> struct Engine : EngineBase {
     int normalize_weights_now() {
         // fold the pending 1/||w|| into the stored weights (general path keeps them normalised)
         if (!w_pending) return 0;
+        w_outside_scan = true;        // (a non-finite scale -- all weights zero -- turns the zeros of every column into NaN)
         hipLaunchKernelGGL(scale_weights_kernel<R>, dim3(ew_blocks, B), dim3(256), 0, stream, w, (const R*)wscale, P);
         HIPCHK(hipGetLastError());
         return fill_wscale_one();
@@ -1566,7 +1573,7 @@ template <typename R> struct Engine : EngineBase {
         f.Ph = g.Ph; f.Pw = g.Pw; f.B = B; f.n_cu = n_cu; f.col_blocks = col_blocks; f.tile_blocks = tile_blocks; f.r0 = g.r0; f.Sh = g.Sh;
         f.stat_groups = stat_ctx ? stat_ctx->groups : 0;
         f.w_unit = w_unit;
-        f.sparse_tiles = sparse_tiles; f.sparse_dirty = sparse_dirty;
+        f.sparse_tiles = sparse_tiles; f.sparse_dirty = sparse_dirty; f.w_outside_scan = w_outside_scan;
         f.n_active_min = n_active_min; f.n_active_max = n_active_max; f.n_noise_max = n_noise_max; f.n_signal_max = n_signal_max;
         f.tun = tun;
         return f;
@@ -1629,6 +1636,7 @@ template <typename R> struct Engine : EngineBase {
         n_active_max = *std::max_element(h.begin(), h.end());
         n_active_min = *std::min_element(h.begin(), h.end());
         sparse_dirty = false;
+        w_outside_scan = false;
         dil_valid = false;
         noise_valid = false;
         signal_valid = false;
@@ -2226,6 +2234,7 @@ template <typename R> struct Engine : EngineBase {
         };
         farfield_valid = false;
         w_unit = false;           // (spot_update writes the weights itself)
+        w_outside_scan = true;
         Plan p = plan_iteration(st, hist ? hist : nullptr);
         if (int e = keep_prev_phase(p, n)) return e;
         if (!gh_holds(windows_needed(p) ? 2 : 1)) { if (int e = run_row(0, false, 0, windows_needed(p) ? 2 : 1)) return e; }
@@ -2300,9 +2309,14 @@ template <typename R> struct Engine : EngineBase {
             // single-pass MRAF: which columns hold a NaN target (the noise part exists only there) -- a fact about the
             // target, scanned once per upload; the dense launches themselves still walk every column
             if (int e = refresh_sparse()) return e;
-        } else if (sizeof(R) == 4 && g.Ph == 4096 && B == 1 && tun.tile2) {
+        } else if (sizeof(R) == 4 && tun.tile2 && g.Ph == 4096 && (B == 1 || (tun.empty_col_loads && !st->mraf_enabled))) {
             // dense launches of one hologram at 4096 rows: how many columns hold anything picks the instance of the half-width
             // tile kernel (ColArgs::few_active) -- a fact about the target, scanned once per upload
+            // (batches: the same scan says in which columns that kernel requests weights and targets at all; they now pay it
+            //  too -- one scan launch and a device-to-host synchronisation per upload of weights or target, dense images included)
+            // (weights written behind the scan's back since -- spot feedback, a folded scale -- are scanned again here, once,
+            //  so that the flags are withheld for no longer than it takes to reach this line)
+            if (w_outside_scan && tun.empty_col_loads) sparse_dirty = true;
             if (int e = refresh_sparse()) return e;
         }
         // "computational_spot" statistics on the sparse path: amp_ff is produced on the spot columns dilated
@@ -2601,6 +2615,7 @@ template <typename R> struct Engine : EngineBase {
             case HGS_OPT_SEPARABLE: opt_separable = value ? 1 : 0; return 0;
             case HGS_OPT_SEPARABLE_MIN_SPOTS: opt_sep_min = value > 0 ? value : 1; return 0;
             case HGS_OPT_RUN_KERNELS: opt_run = value ? 1 : 0; return 0;
+            case HGS_OPT_EMPTY_COL_LOADS: tun.empty_col_loads = value ? 1 : 0; return 0;
             case HGS_OPT_KEEP_PREV_PHASE: opt_prev_phase = value ? 1 : 0; if (!value) have_prev = false; return 0;
             case HGS_OPT_ROCTX:
                 if (value && !g_roctx.load()) return fail(HGS_ERR_UNSUPPORTED, "no roctx library (librocprofiler-sdk-roctx / libroctx64) found");

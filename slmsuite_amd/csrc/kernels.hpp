@@ -1005,7 +1005,8 @@ template <typename R> struct ColArgs {
     int col_xmap;          // dense launches of col_fused_kernel with fewer than four columns per pass: the passes of one
                            // 4-column tile go to workgroups of ONE XCD that run together (gridDim.x a multiple of 8 * PASSES)
     const unsigned char* col_flags;   // [batch][Pw] scan_active_cols bits, or nullptr (col_tile_kernel RULE 4 skips the inverse
-                                      // transforms of the parts that are zero in a column)
+                                      // transforms of the parts that are zero in a column; col_tile2_kernel
+                                      // requests weights / targets only in the columns whose bit 0 is set)
     const int* col_list;   // [batch][Pw] compacted active columns
     const int* n_active;   // [batch]
     // fused kernels only: statistics of this iteration (hgs_iterate_stats)
@@ -1644,6 +1645,30 @@ __device__ __forceinline__ void issue_wt_loads(const R* __restrict__ wc, const R
         wr[m] = wc[lane_pos<T>(j, m)];
         tr[m] = upd ? tc[lane_pos<T>(j, m)] : (R)0;
     });
+}
+
+// ... through buffer resources of `bytes` bytes (col_tile2_kernel with the column flags of the scan): the column's bytes where the
+// scan found a non-zero weight or target in it, 0 where it did not -- an empty resource returns zeros, which is what the column
+// holds, and fetches nothing.  Straight-line like the plain form (a uniform branch around the loads would put a vmcnt(0) at its
+// join); the lane's 64 contiguous bytes as four 16-byte requests per array, the quarter in the SGPR offset (which the range
+// check ignores: a flagged column's resource covers every lane's 64 bytes, an empty one nothing).
+template <typename R, int T>
+__device__ __forceinline__ void issue_wt_loads_buf(const R* __restrict__ wc, const R* __restrict__ tc, unsigned bytes, bool upd, int j,
+                                                   R (&wr)[16], R (&tr)[16]) {
+    static_assert(sizeof(R) == 4, "issue_wt_loads_buf: 16 values of a lane are 64 bytes");
+    if (HGS_ABL_WT != 0) { issue_wt_loads<R, T>(wc, tc, upd, j, wr, tr); return; }      // (ablation builds: constants, no loads)
+    const Buf bw(wc, bytes), bt(tc, bytes);
+    const unsigned vo = lane_pos<T>(j, 0) * (unsigned)sizeof(R);
+    float4 wq[4], tq[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wq[k] = bw.template ld<float4>(vo, 16u * k);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tq[k] = upd ? bt.template ld<float4>(vo, 16u * k) : make_float4(0, 0, 0, 0);   // (upd: a constant of the instance)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        wr[4 * k] = wq[k].x; wr[4 * k + 1] = wq[k].y; wr[4 * k + 2] = wq[k].z; wr[4 * k + 3] = wq[k].w;
+        tr[4 * k] = tq[k].x; tr[4 * k + 1] = tq[k].y; tr[4 * k + 2] = tq[k].z; tr[4 * k + 3] = tq[k].w;
+    }
 }
 
 // an empty asm statement that names the registers: whatever request fills them is waited for HERE (col_tile_kernel TOUCH)
@@ -2353,6 +2378,24 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
         half = (int)blockIdx.x & 1; ct0 = (int)blockIdx.x >> 1; ct_step = G / 2;
     }
     bool first = true;
+    // Column flags of the scan (a.col_flags; the engine passes them only while the scan is current): bit 0 of a column's byte
+    // says that the column holds a non-zero (or NaN) weight or target.  Every other column is zeros in both arrays, and its
+    // requests go through an EMPTY resource (issue_wt_loads_buf): the registers hold the zeros the loads would have returned,
+    // nothing is fetched.  The in-pass update keeps such a column at zero (w = 0, t = 0: the wave-uniform skip below), so the
+    // flags stay true for the lifetime of the loop.  The four bytes of a tile are read as ONE aligned word through the scalar
+    // cache, the next tile's a half tile ahead; fw / fwn = -1 means "fetch every column".
+    // Which instances: 4096 rows, the parked next-tile-ahead form (NXF: few-active targets only, always the resource form) and
+    // the register form of batches, which takes the resource form only when flags arrive (wt_buf) and the plain loads
+    // otherwise -- dense images, many active columns, the option off.  The parked form without NXF and the 2048-row form
+    // never receive flags (NOTEBOOK.md, "Column flags").
+    // (at most five slots, like NXF: with six the register form that holds both load forms keeps 4 spilled registers, 2 more than
+    //  with the plain loads alone)
+    constexpr bool WTBUF = N == 4096 && NR <= 5 && (NXF || !PARK);
+    const unsigned col_bytes = (unsigned)g.Ph * (unsigned)sizeof(R);
+    const int* cflag4 = (WTBUF && a.col_flags != nullptr) ? reinterpret_cast<const int*>(a.col_flags + (size_t)b * g.Pw) : nullptr;
+    int fw = -1, fwn = -1;                       // scan bytes of this tile / of the group's next one (-1: every column fetched)
+    const bool wt_buf = WTBUF && (NXF || cflag4 != nullptr);        // (uniform; NXF: a constant)
+    if constexpr (WTBUF) { if (cflag4 != nullptr && ct0 < ntiles) fw = uniform_load_i32(cflag4 + ct0); }
     // PARK: the rows of the workgroup's NEXT half tile are requested BEFORE the stores of the current one (vmcnt retires in order:
     // behind the stores, the wait for the new rows also waited for the stores to be acknowledged -- tools/microbench/trace_tile2:
     // 6.3 k cycles per half tile); they travel in the registers the finished tile has just freed
@@ -2408,8 +2451,14 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
 #endif
         HGS_T(fft.tr_n, 2);
         const int col0 = ct * 4 + 2 * half;
+        const bool more = ct + ct_step < ntiles;
+        if constexpr (WTBUF) { if (cflag4 != nullptr && more) fwn = uniform_load_i32(cflag4 + ct + ct_step); }
         if (first) {
-            issue_wt_loads<R, T>(wbase + (size_t)col0 * g.Ph, tbase + (size_t)col0 * g.Ph, do_upd, j, wr, tr);
+            if (wt_buf)
+                issue_wt_loads_buf<R, T>(wbase + (size_t)col0 * g.Ph, tbase + (size_t)col0 * g.Ph,
+                                         ((fw >> (16 * half)) & 1) ? col_bytes : 0u, do_upd, j, wr, tr);
+            else
+                issue_wt_loads<R, T>(wbase + (size_t)col0 * g.Ph, tbase + (size_t)col0 * g.Ph, do_upd, j, wr, tr);
             first = false;
         }
 #pragma unroll 1
@@ -2494,9 +2543,17 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 static_for<0, 16>([&](auto m_) { constexpr int m = m_; wc[lane_pos<T>(j, m)] = wr[m]; });
             }
             {   // weights / target of the next column (or of the first column of this group's next half tile)
-                const int ncol = c == 0 ? col0 + 1 : (ct + ct_step) * 4 + 2 * half;
-                if (c == 0 || ct + ct_step < ntiles)
-                    issue_wt_loads<R, T>(wbase + (size_t)ncol * g.Ph, tbase + (size_t)ncol * g.Ph, do_upd, j, wr, tr);
+                if (wt_buf) {
+                    // (straight-line: no next half tile = an empty resource on this column)
+                    const int ncol = c == 0 ? col0 + 1 : more ? (ct + ct_step) * 4 + 2 * half : col0;
+                    const int nflag = c == 0 ? fw >> (16 * half + 8) : more ? fwn >> (16 * half) : 0;
+                    issue_wt_loads_buf<R, T>(wbase + (size_t)ncol * g.Ph, tbase + (size_t)ncol * g.Ph, (nflag & 1) ? col_bytes : 0u,
+                                             do_upd, j, wr, tr);
+                } else {
+                    const int ncol = c == 0 ? col0 + 1 : (ct + ct_step) * 4 + 2 * half;
+                    if (c == 0 || more)
+                        issue_wt_loads<R, T>(wbase + (size_t)ncol * g.Ph, tbase + (size_t)ncol * g.Ph, do_upd, j, wr, tr);
+                }
             }
             HGS_T(fft.tr_n, 5);
             fft.template inv_after_fwd_trail<NR>(v, lds, j);
@@ -2558,6 +2615,7 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 }
             }
         }
+        fw = fwn;
     }
     HGS_T(fft.tr_n, 7);
     if constexpr (do_upd) {

@@ -42,7 +42,7 @@ template <typename R> inline unsigned row_flags(dim3 grid, const RowArgs<R>& a) 
 }
 template <typename R> inline unsigned col_flags(dim3 grid, const ColArgs<R>& a) {
     return (a.col_list ? DF_LIST : 0u) | ((a.col_list ? a.list_xmap : a.col_xmap) ? DF_XMAP : 0u) | (grid.y > 1 ? DF_BATCH : 0u) |
-           (a.do_stats ? DF_STATS : 0u);
+           (a.do_stats ? DF_STATS : 0u) | (a.col_flags ? DF_COL_FLAGS : 0u);
 }
 
 // returns hipError_t as int
