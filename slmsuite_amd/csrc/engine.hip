@@ -15,6 +15,8 @@
 #include "../../include/hgs.h"
 #include "launch.hpp"
 #include "column_plan.hpp"
+#include "devbuf.hpp"
+#include "engine_state.hpp"
 #include "compressed_kernels.hpp"
 #include "cgemm.hpp"
 #include "compressed_sep.hpp"
@@ -132,6 +134,26 @@ static int env_int(const char* name, int dflt) {
     return v ? atoi(v) : dflt;
 }
 
+// A compacted list of columns: those whose flag byte (scan_active_cols, dilate_active_cols) has one of the bits of `bit`
+// set.  Whether a list still matches the scan it was built from is the EngineState's business, not the list's.
+struct ColList {
+    DevBuf<int> list;               // [B][Pw] compacted
+    DevBuf<int> n_dev;              // [B] how many of them
+    DevBuf<unsigned short> mask;    // [B][Pw/16] row-kernel view of the same columns
+    int n_max = 0, n_min = 0;       // over the holograms of the batch
+    int build(const unsigned char* flags, int bit, int B, int Pw, hipStream_t stream) {
+        HIPCHK(list.ensure((size_t)B * Pw)); HIPCHK(n_dev.ensure((size_t)B)); HIPCHK(mask.ensure((size_t)B * (Pw / 16)));
+        hipLaunchKernelGGL(compact_active_cols, dim3(B), dim3(256), 0, stream, flags, Pw, list.get(), n_dev.get(), mask.get(), bit);
+        HIPCHK(hipGetLastError());
+        std::vector<int> h(B);
+        HIPCHK(hipMemcpyAsync(h.data(), n_dev, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        n_max = *std::max_element(h.begin(), h.end());
+        n_min = *std::min_element(h.begin(), h.end());
+        return 0;
+    }
+};
+
 struct EngineBase {
     int device = 0;      // HIP device ordinal of this engine; every C-ABI entry makes it current first
     DispatchLog dispatch;    // kernel instances launched since the last hgs_dispatch_read
@@ -175,53 +197,29 @@ template <typename R> struct Engine : EngineBase {
     size_t S = 0, P = 0;  // elements per hologram
     int B = 1;
     // device buffers
-    R* phase = nullptr;
-    R* amp = nullptr;
-    R* kern = nullptr;
-    C* gh = nullptr;
-    C* gh2 = nullptr;         // single-pass MRAF: the noise-region part of the field between the column and the row kernel
-    R* w = nullptr;
-    R* t = nullptr;
-    R* pff = nullptr;
-    C* ff = nullptr;
-    R* aff = nullptr;
-    C* zw = nullptr;
-    void* staging = nullptr;  // B*P complex, natural-layout bounce buffer for set/get
-    C* tw_row = nullptr;
+    DevBuf<R> phase, amp, kern, w, t, pff, aff, wscale;
+    DevBuf<C> gh, ff, zw;
+    DevBuf<C> gh2;         // single-pass MRAF: the noise-region part of the field between the column and the row kernel
+    DevBuf<char> staging;  // B*P complex, natural-layout bounce buffer for set/get
+    DevBuf<C> tw_row, tw_col_own;     // square pads share one table: tw_col is tw_row then, else tw_col_own
     C* tw_col = nullptr;
-    double* wpartial = nullptr;
-    double* dpartial = nullptr;  // partials of col_presum_kernel (single-inverse MRAF), sized like wpartial
-    double* fpartial = nullptr;
-    double* epartial = nullptr;  // elementwise partials
-    double* sums = nullptr;      // [3][B]: fsum, nogsum, wsum
-    R* wscale = nullptr;
-    int* spot_xy = nullptr;
-    double* spot_amp = nullptr;
-    double* ext_amp = nullptr;
-    R* spot_fb = nullptr;
-    C* nfbuf = nullptr;               // [B][Sh][Sw] complex nearfield of f2n_complex (MultiplaneHologram)
-    R* nog_dev = nullptr;             // [B] -1/mean(fc) of the fused WGS-Nogrette pass
+    DevBuf<double> wpartial, fpartial;
+    DevBuf<double> dpartial;  // partials of col_presum_kernel (single-inverse MRAF), sized like wpartial
+    DevBuf<double> epartial;  // elementwise partials
+    DevBuf<double> sums;      // [3][B]: fsum, nogsum, wsum
+    DevBuf<int> spot_xy;
+    DevBuf<double> spot_amp, ext_amp;
+    DevBuf<R> spot_fb;
+    DevBuf<C> nfbuf;               // [B][Sh][Sw] complex nearfield of f2n_complex (MultiplaneHologram)
+    DevBuf<R> nog_dev;             // [B] -1/mean(fc) of the fused WGS-Nogrette pass
     // sparse targets (spot arrays): columns that hold a non-zero weight or target
-    unsigned char* col_active = nullptr;   // [B][Pw]
-    unsigned short* sig_rows = nullptr;    // [B][Pw] register slots of a column that hold signal pixels (scan_active_cols; col_presum_kernel)
-    int* col_list = nullptr;               // [B][Pw] compacted
-    int* n_active_dev = nullptr;           // [B]
-    unsigned short* lane_mask = nullptr;   // [B][Pw/16] row-kernel view of col_active
-    unsigned short* lane_mask_noise = nullptr;   // ... of its bit 4: columns with a NaN target (noise part of single-pass MRAF)
+    DevBuf<unsigned char> col_active;   // [B][Pw]
+    DevBuf<unsigned short> sig_rows;    // [B][Pw] register slots of a column that hold signal pixels (scan_active_cols; col_presum_kernel)
+    ColList active;                     // any bit of col_active
+    DevBuf<unsigned short> lane_mask_noise;   // row-kernel view of its bit 4: columns with a NaN target (noise part of single-pass MRAF)
     // the same for the columns the spot integration windows touch (spot feedback / spot statistics)
-    unsigned char* col_active_d = nullptr;
-    int* col_list_d = nullptr;
-    int* n_active_d_dev = nullptr;
-    unsigned short* lane_mask_d = nullptr;
-    int n_active_d_max = 0, dil_lo = 0, dil_hi = 0;
-    bool dil_valid = false;
-    int n_active_max = 0, n_active_min = 0;
-    bool sparse_dirty = true;
-    // spot_update (the N-vector rule) has written weights at the spot pixels since the last column scan: a spot whose target
-    // and weight were zero then sits in a column the scan found empty, and a NaN factor turns its weight into 1e-4.  The column
-    // lists keep their meaning (such a pixel never had a target), the per-column load flags of col_tile2_kernel are withheld
-    // until the next scan, which the next dense call that could use them runs itself (iterate()).
-    bool w_outside_scan = false;
+    DevBuf<unsigned char> col_active_d;
+    ColList dilated;
     bool sparse_tiles = false;             // the active set is whole 4-column tiles (the tile-resident kernel walks the list)
     // engine policy (hgs_set_option) and the developer switches, read from the environment once, in init() (read_tuning)
     Tuning tun;
@@ -229,85 +227,68 @@ template <typename R> struct Engine : EngineBase {
     int opt_separable = 1;                 // HGS_OPT_SEPARABLE
     int opt_sep_min = 96;                  // smallest spot count the matrix-core form is used for (tools/sep_crossover.py)
     int opt_roctx = 0;                     // HGS_OPT_ROCTX: roctx ranges around the operators
-    // G left behind (round 5): the last launch of a fused float32 hgs_iterate call is row_kernel MODE 3 -- it writes the phase AND
-    // the row-transformed field of the next body, every column of it -- and the next call (or hgs_nearfield2farfield) skips its
-    // own first row launch while nothing that G depends on (phase, amplitude, kernel) has changed.
-    //   gh_state: -1 = gh does not hold G; 0 = G of every column; 1 = of the active columns; 2 = of the dilated active columns
-    int gh_state = -1;
+    // what the buffers currently hold (G left behind, farfield, phase_ff, the weights' norm, the column lists): engine_state.hpp
+    EngineState state;
     // HGS_OPT_KEEP_PREV_PHASE: the phase a one-iteration fused call started from (what its farfield phase describes)
-    R* phase_prev = nullptr;
-    bool have_prev = false;
+    DevBuf<R> phase_prev;
     int opt_prev_phase = 0;
     // hgs_cg_iterate (optimize(method="CG")): Adam moments and the last gradient over the SLM window, the partial sums of the
     // seed pass and one loss per body of the running call; all allocated by the first call.  cg_t: Adam's step counter
-    R* cg_m = nullptr;
-    R* cg_v = nullptr;
-    R* cg_grad = nullptr;
-    double* cg_partial = nullptr;      // [ew_blocks]
-    double* cg_loss = nullptr;         // [cg_loss_cap] sum r^2 of each body
+    DevBuf<R> cg_m, cg_v, cg_grad;
+    DevBuf<double> cg_partial;      // [ew_blocks]
+    DevBuf<double> cg_loss;         // [cg_loss_cap] sum r^2 of each body
     int cg_loss_cap = 0, cg_t = 0;
-    bool cg_have_grad = false;
     // hgs_remove_vortices: per-block counts / offsets of the search, the list (x, y, w) of the last call (grown to the
     // count the host reads once per call) and that count, device resident for the removal; vx_n: the host's copy, -1 = no call yet
-    unsigned* vx_counts = nullptr;
-    int32_t* vx_list = nullptr;
-    int32_t* vx_count = nullptr;
+    DevBuf<unsigned> vx_counts;
+    DevBuf<int32_t> vx_list, vx_count;
     unsigned vx_cap = 0;
     int vx_n = -1;
     // per-column kernel (float64; float32 where the tile-resident kernel does not run) single-pass MRAF: noise part as farfield
     // values, the columns that hold it, their inverse pass
-    C* ffb = nullptr;                      // [B][P], layout of ff; only NaN-target pixels are ever written, the rest stays zero
-    int* col_list_noise = nullptr;         // [B][Pw] columns with a NaN target (bit 4 of col_active), compacted
-    int* n_noise_dev = nullptr;            // [B]
-    unsigned short* lane_mask_tmp = nullptr;
-    int n_noise_max = 0;
-    bool noise_valid = false;              // col_list_noise matches the current target
-    int* col_list_signal = nullptr;        // [B][Pw] columns with a finite non-zero target (bit 1 of col_active), compacted: the
-    int* n_signal_dev = nullptr;           // [B]     per-column pre-pass of the single-inverse MRAF update walks them
-    int n_signal_max = 0;
-    bool signal_valid = false;
-    bool ffb_zeroed = false;               // ... and so do the zeros of ffb (written since at NaN-target pixels only)
+    DevBuf<C> ffb;                      // [B][P], layout of ff; only NaN-target pixels are ever written, the rest stays zero
+    ColList noise;                      // columns with a NaN target (bit 4 of col_active); its mask is not used
+    ColList signal;                     // columns with a finite non-zero target (bit 1 of col_active): the per-column pre-pass of
+                                        // the single-inverse MRAF update walks them; its mask is not used
     int row_blocks_pref = 0;               // its grid: two workgroups per CU, whole XCD line groups
     // statistics of the fused path (hgs_iterate_stats)
-    double* stats_scratch = nullptr;  // hgs_stats group 0: per-block partials of the two passes
-    int* stats_dxy = nullptr;         // hgs_stats group 1: floor(spot_knm)
-    double* stat_partial = nullptr;   // [B][blocks][STAT_WAVES][STAT_N]
-    double* stat_tsum = nullptr;      // [B] sum T^2
-    struct StatCtx { int groups = 0, width = 1; double* dev_out = nullptr; int* dxy = nullptr; };
+    DevBuf<double> stats_scratch;  // hgs_stats group 0: per-block partials of the two passes
+    DevBuf<int> stats_dxy;         // hgs_stats group 1: floor(spot_knm)
+    DevBuf<double> stat_partial;   // [B][blocks][STAT_WAVES][STAT_N]
+    DevBuf<double> stat_tsum;      // [B] sum T^2
+    struct StatCtx { int groups = 0, width = 1; DevBuf<double> dev_out; DevBuf<int> dxy; };
     StatCtx* stat_ctx = nullptr;      // non-null while hgs_iterate_stats drives the fused loop
     size_t stat_nslots = 0;
     // padded shapes that are not powers of two in [64, 8192]: Bluestein path (bluestein.hpp)
     bool general = false;
     int blue_M[2] = {0, 0};            // convolution lengths for x (rows, N = Pw) and y (columns, N = Ph)
     bool blue_plain[2] = {false, false};   // the axis is a power of two: M = N, no convolution
-    C* blue_tab[2][2][3] = {};         // [x|y][forward|inverse][A, Bf, Cc]
+    DevBuf<C> blue_tab[2][2][3];       // [x|y][forward|inverse][A, Bf, Cc]
+    DevBuf<C> blue_tw_own[2];          // equal convolution lengths share one table: blue_tw[1] is blue_tw[0] then
     C* blue_tw[2] = {nullptr, nullptr};
     // kind 1 (compressed)
-    R* xg = nullptr;
-    R* yg = nullptr;
-    int* mono = nullptr;
-    R* coeff = nullptr;
-    Cx<R>* cpartial = nullptr;
-    double* cnorm = nullptr;
-    R* ext_r = nullptr;
+    DevBuf<R> xg, yg, coeff, ext_r;
+    DevBuf<int> mono;
+    DevBuf<Cx<R>> cpartial;
+    DevBuf<double> cnorm;
     int c_nblocks = 0, c_degree = -1, c_rows = 0;
     // separable (matrix-core) form of the compressed transforms, fp32 only (compressed_sep.hpp)
     bool grid_sep[2] = {false, false}, c_sep = false;
     std::vector<double> xs_host, ys_host;
-    double* sep_c = nullptr;        // [2][SEP_MAXDEG+1][N] polynomial coefficients of fx_n, fy_n
-    double* sep_g = nullptr;        // xs[W] then ys[H]
-    float2* sep_ex = nullptr;       // [N][W]
-    float2* sep_exT = nullptr;      // [W][N]
-    float2* sep_ey = nullptr;       // [N][H]
-    float2* sep_nfT = nullptr;      // [B][W][H]
-    float2* sep_b2 = nullptr;       // [B][N][H]
-    float2* sep_c1 = nullptr;       // [B][tiles_n1 * 2 * split1][Np] partial y contractions of the n2f GEMM epilogue
-    float2* sep_c2 = nullptr;       // [B][split2][H][W]
-    double* sep_norm = nullptr;     // [B][ceil(N/4)]
+    DevBuf<double> sep_c;        // [2][SEP_MAXDEG+1][N] polynomial coefficients of fx_n, fy_n
+    DevBuf<double> sep_g;        // xs[W] then ys[H]
+    DevBuf<float2> sep_ex;       // [N][W]
+    DevBuf<float2> sep_exT;      // [W][N]
+    DevBuf<float2> sep_ey;       // [N][H]
+    DevBuf<float2> sep_nfT;      // [B][W][H]
+    DevBuf<float2> sep_b2;       // [B][N][H]
+    DevBuf<float2> sep_c1;       // [B][tiles_n1 * 2 * split1][Np] partial y contractions of the n2f GEMM epilogue
+    DevBuf<float2> sep_c2;       // [B][split2][H][W]
+    DevBuf<double> sep_norm;     // [B][ceil(N/4)]
     int sep_split1 = 1, sep_kper1 = 0, sep_split2 = 1, sep_kper2 = 0, sep_degx = 0, sep_degy = 0;
     // stream-K schedule of the two GEMMs (cgemm_streamk): sep_split1 / sep_split2 are then the partial planes of C
     int sk_G1 = 0, sk_G2 = 0, sk_kt1 = 0, sk_kt2 = 0, sk_tm1 = 0, sk_tn1 = 0, sk_tm2 = 0, sk_tn2 = 0;
-    int* sk_tab = nullptr;          // [first_wg 1][nseg 1][first_wg 2][nseg 2]
+    DevBuf<int> sk_tab;          // [first_wg 1][nseg 1][first_wg 2][nseg 2]
     int sep_Np = 0, sep_Hp = 0, sep_Wp = 0, sep_Wk = 0, sep_Nk = 0;   // padded leading dimensions / row counts
     std::vector<int32_t> mono_host;
     std::vector<R> coeff_host;
@@ -315,20 +296,14 @@ template <typename R> struct Engine : EngineBase {
     // run kernels of the direct compressed transforms (compressed_kernels.hpp: regular grid, degree <= 2, fp32)
     bool run_ok = false;
     int opt_run = 1;                       // HGS_OPT_RUN_KERNELS
-    CRunRec* run_rec = nullptr;            // [N]
-    double* run_ys = nullptr;              // [H]
-    Cx<float>* run_nf = nullptr;           // [B][run_chunks][S]
+    DevBuf<CRunRec> run_rec;            // [N]
+    DevBuf<double> run_ys;              // [H]
+    DevBuf<Cx<float>> run_nf;           // [B][run_chunks][S]
     double run_x0 = 0, run_hx = 0;
     int run_rpr = 0, run_blocks = 0, run_chunks = 1, run_nper = 0, run_nf_chunks = 0;
     // host state
     double amp_scalar = 0, amp_norm2 = 1.0;
-    bool has_amp = false, has_kern = false, have_pff = false, farfield_valid = false;
-    bool w_pending = false;  // weights stored un-normalised, wscale holds 1/||w||
-    // ... and wscale^2 * sum w^2 = 1 to rounding: the stored weights were last written by an update pass of the fused loop and
-    // wscale was folded from THAT pass' partial sums (no NaN left among them).  What the single-inverse MRAF pass builds on
-    // (||w'||^2 = 1 + D); every other writer of the weights or of wscale goes through fill_wscale_one and clears it.
-    bool w_unit = false;
-    bool has_target = false, has_spots = false;
+    bool has_amp = false, has_kern = false, has_target = false, has_spots = false;
     int row_blocks = 0, col_blocks = 0, ew_blocks = 0, n_cu = 256, row_xcd = 0, tile_blocks = 0, col_xmap = 0;
     // profiling
     bool prof = false;
@@ -337,16 +312,10 @@ template <typename R> struct Engine : EngineBase {
     double prof_ms[HGS_K_COUNT] = {0};
     double prof_n[HGS_K_COUNT] = {0};
 
+    // The buffers are DevBuf members: they free themselves after this body, i.e. after hipStreamDestroy.  The stream is
+    // drained first, so nothing uses them any more, and hipFree does not depend on the current device (hgs_destroy sets none).
     ~Engine() override {
         if (stream) hipStreamSynchronize(stream);
-        if (tw_col == tw_row) tw_col = nullptr;
-        void* ptrs[] = {vx_counts, vx_list, vx_count, cg_m, cg_v, cg_grad, cg_partial, cg_loss, phase_prev, ffb, col_list_signal, n_signal_dev, col_list_noise, n_noise_dev, lane_mask_tmp, lane_mask_noise, phase, amp, kern, gh, gh2, w, t, pff, ff, aff, zw, staging, tw_row, tw_col, wpartial, dpartial,
-                        fpartial, epartial, sums, wscale, spot_xy, spot_amp, ext_amp, spot_fb, nfbuf, nog_dev, stats_scratch, stats_dxy, col_active, sig_rows, col_list, n_active_dev, lane_mask, col_active_d, col_list_d, n_active_d_dev, lane_mask_d, stat_partial, stat_tsum, xg, yg, mono, coeff, cpartial, cnorm, ext_r, sep_c, sep_g, sep_ex, sep_exT, sep_ey, sep_nfT, sep_b2, sep_c1, sep_c2, sep_norm, run_rec, run_ys, run_nf, sk_tab};
-        for (void* p : ptrs)
-            if (p) hipFree(p);
-        for (auto& d : blue_tab) for (auto& dir : d) for (C* t3 : dir) if (t3) hipFree(t3);
-        if (blue_tw[0]) hipFree(blue_tw[0]);
-        if (blue_tw[1] && blue_tw[1] != blue_tw[0]) hipFree(blue_tw[1]);
         for (auto& e : evs) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
         for (hipEvent_t ev : timed_ev) if (ev) hipEventDestroy(ev);
         if (stream) hipStreamDestroy(stream);
@@ -359,13 +328,18 @@ template <typename R> struct Engine : EngineBase {
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }
-    template <typename T> int dalloc(T** p, size_t n) {
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-        HIPCHK(hipMemsetAsync(*p, 0, n * sizeof(T), stream));
+    // device -> host (or device), complete on return
+    int d2h(void* dst, const void* src, size_t nbytes, bool dst_device = false) {
+        HIPCHK(hipMemcpyAsync(dst, src, nbytes, dst_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }
+    // n zeroed elements (the memset on the engine stream); need / need_zeroed: by the first call that uses the buffer
+    template <typename T> int dalloc(DevBuf<T>& b, size_t n) { HIPCHK(b.alloc_zeroed(n, stream)); return 0; }
+    template <typename T> int need(DevBuf<T>& b, size_t n) { HIPCHK(b.ensure(n)); return 0; }
+    template <typename T> int need_zeroed(DevBuf<T>& b, size_t n) { HIPCHK(b.ensure_zeroed(n, stream)); return 0; }
 
-    int make_twiddles(C** dev, int N) {
+    int make_twiddles(DevBuf<C>& dev, int N) {
         std::vector<C> h(N);
         for (int i = 0; i < N; ++i) {
             const double a = -2.0 * M_PI * (double)i / (double)N;
@@ -377,9 +351,8 @@ template <typename R> struct Engine : EngineBase {
         h[N / 4].x = 0; h[N / 4].y = -1;
         h[N / 2].x = -1; h[N / 2].y = 0;
         h[3 * N / 4].x = 0; h[3 * N / 4].y = 1;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(dev), N * sizeof(C)));
-        if (int e_ = h2d(*dev, h.data(), N * sizeof(C))) return e_;
-        return 0;
+        HIPCHK(dev.alloc(N));
+        return h2d(dev, h.data(), N * sizeof(C));
     }
 
     // the developer switches, in the order include/hgs.h lists them: the one place the environment is read
@@ -512,35 +485,37 @@ template <typename R> struct Engine : EngineBase {
         tile_blocks = std::max(1, std::min(tiles, tun.tile_blocks / B));
         ew_blocks = (int)std::min<size_t>((P + 255) / 256, (size_t)std::max(1, n_cu * 8 / B));
 
-        if (dalloc(&phase, B * S)) return HGS_ERR_DEVICE;
+        if (dalloc(phase, B * S)) return HGS_ERR_DEVICE;
         lap("phase");
-        if (dalloc(&gh, (size_t)B * g.Sh * g.Pw)) return HGS_ERR_DEVICE;
+        if (dalloc(gh, (size_t)B * g.Sh * g.Pw)) return HGS_ERR_DEVICE;
         lap("gh");
-        if (dalloc(&w, B * P)) return HGS_ERR_DEVICE;
-        if (dalloc(&t, B * P)) return HGS_ERR_DEVICE;
+        if (dalloc(w, B * P) || dalloc(t, B * P)) return HGS_ERR_DEVICE;
         lap("weights + target");
-        if (dalloc(&wpartial, (size_t)B * std::max(std::max(col_blocks, tile_blocks), n_cu * 3))) return HGS_ERR_DEVICE;
-        if (dalloc(&fpartial, (size_t)B * std::max(col_blocks, n_cu * 3))) return HGS_ERR_DEVICE;
-        if (dalloc(&epartial, (size_t)B * ew_blocks)) return HGS_ERR_DEVICE;
-        if (dalloc(&sums, (size_t)4 * B)) return HGS_ERR_DEVICE;
-        if (dalloc(&wscale, (size_t)B)) return HGS_ERR_DEVICE;
-        if (int e = fill_wscale_one()) return e;
+        if (int e = alloc_partials((size_t)B * std::max(std::max(col_blocks, tile_blocks), n_cu * 3), (size_t)B * std::max(col_blocks, n_cu * 3))) return e;
         lap("partials");
-        if (int e = make_twiddles(&tw_row, g.Pw)) return e;
-        if (g.Ph == g.Pw) tw_col = tw_row;                    // square pads: one table
-        else if (int e = make_twiddles(&tw_col, g.Ph)) return e;
+        if (int e = make_twiddles(tw_row, g.Pw)) return e;
+        if (g.Ph != g.Pw) { if (int e = make_twiddles(tw_col_own, g.Ph)) return e; }
+        tw_col = g.Ph == g.Pw ? tw_row : tw_col_own;          // square pads: one table
         lap("twiddles");
-        if (c.n_spots > 0) {
-            if (dalloc(&spot_xy, (size_t)2 * c.n_spots)) return HGS_ERR_DEVICE;
-            if (dalloc(&spot_amp, (size_t)c.n_spots)) return HGS_ERR_DEVICE;
-            if (dalloc(&ext_amp, (size_t)c.n_spots)) return HGS_ERR_DEVICE;
-            if (dalloc(&spot_fb, (size_t)B * c.n_spots)) return HGS_ERR_DEVICE;
-        }
+        if (int e = alloc_spots(c.n_spots)) return e;
         lap("spots");
-        amp_scalar = 1.0 / std::sqrt((double)S);  // Hologram.__init__ :401-402
-        amp_norm2 = 1.0;
         HIPCHK(hipStreamSynchronize(stream));
         lap("sync");
+        return 0;
+    }
+    // the partial sums every kind of engine folds, and wscale = 1; the source amplitude starts as the scalar 1 / sqrt(S)
+    // (Hologram.__init__ :401-402)
+    int alloc_partials(size_t n_wpartial, size_t n_fpartial) {
+        if (dalloc(wpartial, n_wpartial) || dalloc(fpartial, n_fpartial) || dalloc(epartial, (size_t)B * ew_blocks) ||
+            dalloc(sums, (size_t)4 * B) || dalloc(wscale, (size_t)B)) return HGS_ERR_DEVICE;
+        amp_scalar = 1.0 / std::sqrt((double)S);
+        amp_norm2 = 1.0;
+        return fill_wscale_one();
+    }
+    int alloc_spots(int n_spots) {
+        if (n_spots <= 0) return 0;
+        if (dalloc(spot_xy, (size_t)2 * n_spots) || dalloc(spot_amp, (size_t)n_spots) || dalloc(ext_amp, (size_t)n_spots) ||
+            dalloc(spot_fb, (size_t)B * n_spots)) return HGS_ERR_DEVICE;
         return 0;
     }
 
@@ -570,7 +545,7 @@ template <typename R> struct Engine : EngineBase {
     }
     // tables of one centred transform of length N (bluestein.hpp): dir = -1 forward, +1 inverse
     // plain: no chirp (A = pre, Cc = post / sqrt(N), Bf unused but allocated as one element)
-    int make_blue_tables(int N, int M, int dir, bool plain, C** out3) {
+    int make_blue_tables(int N, int M, int dir, bool plain, DevBuf<C>* out3) {
         using cd = std::complex<double>;
         const long long h = N / 2;
         const double sg = dir < 0 ? -1.0 : 1.0;
@@ -596,15 +571,15 @@ template <typename R> struct Engine : EngineBase {
             host_fft(bt);
             for (auto& v : bt) v /= (double)M;
         }
-        auto up = [&](const std::vector<cd>& src, C** dst) -> int {
+        auto up = [&](const std::vector<cd>& src, DevBuf<C>& dst) -> int {
             std::vector<C> hbuf(src.size());
             for (size_t i = 0; i < src.size(); ++i) { hbuf[i].x = (R)src[i].real(); hbuf[i].y = (R)src[i].imag(); }
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(dst), hbuf.size() * sizeof(C)));
-            return h2d(*dst, hbuf.data(), hbuf.size() * sizeof(C));
+            HIPCHK(dst.alloc(hbuf.size()));
+            return h2d(dst, hbuf.data(), hbuf.size() * sizeof(C));
         };
-        if (int e = up(A, &out3[0])) return e;
-        if (int e = up(bt, &out3[1])) return e;
-        return up(Cc, &out3[2]);
+        if (int e = up(A, out3[0])) return e;
+        if (int e = up(bt, out3[1])) return e;
+        return up(Cc, out3[2]);
     }
     int init_general(const hgs_config& c) {
         auto conv_len = [](int N) { if (axis_plain(N)) return N; int M = 256; while (M < 2 * N - 1) M <<= 1; return M; };
@@ -623,32 +598,18 @@ template <typename R> struct Engine : EngineBase {
         }
         ew_blocks = (int)std::min<size_t>((P + 255) / 256, (size_t)std::max(1, n_cu * 8 / B));
         col_blocks = tile_blocks = row_blocks = 1;
-        if (dalloc(&phase, B * S)) return HGS_ERR_DEVICE;
-        if (dalloc(&gh, (size_t)B * g.Sh * g.Pw)) return HGS_ERR_DEVICE;
-        if (dalloc(&nfbuf, B * S)) return HGS_ERR_DEVICE;
-        if (dalloc(&w, B * P)) return HGS_ERR_DEVICE;
-        if (dalloc(&t, B * P)) return HGS_ERR_DEVICE;
-        if (dalloc(&wpartial, (size_t)B * n_cu * 3)) return HGS_ERR_DEVICE;
-        if (dalloc(&fpartial, (size_t)B * std::max(ew_blocks, n_cu * 3))) return HGS_ERR_DEVICE;
-        if (dalloc(&epartial, (size_t)B * ew_blocks)) return HGS_ERR_DEVICE;
-        if (dalloc(&sums, (size_t)4 * B)) return HGS_ERR_DEVICE;
-        if (dalloc(&wscale, (size_t)B)) return HGS_ERR_DEVICE;
-        if (int e = fill_wscale_one()) return e;
+        if (dalloc(phase, B * S) || dalloc(gh, (size_t)B * g.Sh * g.Pw) || dalloc(nfbuf, B * S) || dalloc(w, B * P) || dalloc(t, B * P))
+            return HGS_ERR_DEVICE;
+        if (int e = alloc_partials((size_t)B * n_cu * 3, (size_t)B * std::max(ew_blocks, n_cu * 3))) return e;
         for (int d = 0; d < 2; ++d) {
             const int N = d == 0 ? g.Pw : g.Ph;
             if (d == 1 && blue_M[1] == blue_M[0]) blue_tw[1] = blue_tw[0];
-            else if (int e = make_twiddles(&blue_tw[d], blue_M[d])) return e;
+            else if (int e = make_twiddles(blue_tw_own[d], blue_M[d])) return e;
+            else blue_tw[d] = blue_tw_own[d];
             if (int e = make_blue_tables(N, blue_M[d], -1, blue_plain[d], blue_tab[d][0])) return e;
             if (int e = make_blue_tables(N, blue_M[d], +1, blue_plain[d], blue_tab[d][1])) return e;
         }
-        if (c.n_spots > 0) {
-            if (dalloc(&spot_xy, (size_t)2 * c.n_spots)) return HGS_ERR_DEVICE;
-            if (dalloc(&spot_amp, (size_t)c.n_spots)) return HGS_ERR_DEVICE;
-            if (dalloc(&ext_amp, (size_t)c.n_spots)) return HGS_ERR_DEVICE;
-            if (dalloc(&spot_fb, (size_t)B * c.n_spots)) return HGS_ERR_DEVICE;
-        }
-        amp_scalar = 1.0 / std::sqrt((double)S);
-        amp_norm2 = 1.0;
+        if (int e = alloc_spots(c.n_spots)) return e;
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }
@@ -658,7 +619,7 @@ template <typename R> struct Engine : EngineBase {
         a.in = in; a.out = out; a.in_line = in_line; a.out_line = out_line; a.in_batch = in_batch; a.out_batch = out_batch;
         a.in_stride = in_stride; a.out_stride = out_stride; a.in_start = in_start; a.in_len = in_len;
         a.out_start = out_start; a.out_len = out_len; a.N = dim == 0 ? g.Pw : g.Ph;
-        C** t3 = blue_tab[dim][dir < 0 ? 0 : 1];
+        const DevBuf<C>* t3 = blue_tab[dim][dir < 0 ? 0 : 1];
         a.A = t3[0]; a.Bf = t3[1]; a.Cc = t3[2]; a.tw = blue_tw[dim];
         a.plain = blue_plain[dim] ? (dir < 0 ? 1 : 2) : 0;
         LCHK(launch_bluestein<R>(blue_M[dim], dim3(lines, B), stream, a));
@@ -686,17 +647,16 @@ template <typename R> struct Engine : EngineBase {
         });
         if (r) return r;
         if (int e = reduce(fpartial, ew_blocks, sums + 0 * B)) return e;
-        if (store_pff) have_pff = true;
-        farfield_valid = true;
+        state.farfield_materialised(store_pff != 0);
         return 0;
     }
     int f2n_general(bool complex_only) {
-        if (!ff || !farfield_valid) return fail(HGS_ERR_STATE, "no farfield to transform back");
+        if (!ff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "no farfield to transform back");
         int r = timed(HGS_K_COL_INV, [&]() -> int {
             return blue_pass(1, +1, ff, g.Ph, P, 1, 0, g.Ph, gh, 1, (size_t)g.Sh * g.Pw, g.Pw, g.r0, g.Sh, g.Pw);
         });
         if (r) return r;
-        farfield_valid = false;
+        state.farfield_consumed();
         return timed(HGS_K_ROW, [&]() -> int {
             if (int e = blue_pass(0, +1, gh, g.Pw, (size_t)g.Sh * g.Pw, 1, 0, g.Pw, nfbuf, g.Sw, S, 1, g.c0, g.Sw, g.Sh)) return e;
             if (!complex_only) {
@@ -721,27 +681,13 @@ template <typename R> struct Engine : EngineBase {
         col_blocks = 1; tile_blocks = 1; row_blocks = 1;
         ew_blocks = (int)std::min<size_t>((P + 255) / 256, (size_t)std::max(1, n_cu * 8 / B));
         c_rows = std::max(6, c.n_monomials);
-        if (dalloc(&phase, B * S)) return HGS_ERR_DEVICE;
-        if (dalloc(&w, B * P)) return HGS_ERR_DEVICE;
-        if (dalloc(&t, B * P)) return HGS_ERR_DEVICE;
-        if (dalloc(&xg, S)) return HGS_ERR_DEVICE;
-        if (dalloc(&yg, S)) return HGS_ERR_DEVICE;
-        if (dalloc(&mono, (size_t)2 * c.n_monomials)) return HGS_ERR_DEVICE;
-        if (dalloc(&coeff, (size_t)c_rows * P)) return HGS_ERR_DEVICE;
         run_rpr = (g.Sw + CR_RUN - 1) / CR_RUN;
         run_blocks = (g.Sh * run_rpr + 63) / 64;
-        if (dalloc(&cpartial, (size_t)B * std::max(c_nblocks, run_blocks) * P)) return HGS_ERR_DEVICE;
-        if (dalloc(&cnorm, (size_t)B * ((P + C_RED_SPOTS - 1) / C_RED_SPOTS))) return HGS_ERR_DEVICE;
-        if (dalloc(&ext_amp, P)) return HGS_ERR_DEVICE;
-        if (dalloc(&ext_r, B * P)) return HGS_ERR_DEVICE;
-        if (dalloc(&epartial, (size_t)B * ew_blocks)) return HGS_ERR_DEVICE;
-        if (dalloc(&wpartial, (size_t)B)) return HGS_ERR_DEVICE;
-        if (dalloc(&fpartial, (size_t)B)) return HGS_ERR_DEVICE;
-        if (dalloc(&sums, (size_t)4 * B)) return HGS_ERR_DEVICE;
-        if (dalloc(&wscale, (size_t)B)) return HGS_ERR_DEVICE;
-        if (int e = fill_wscale_one()) return e;
-        amp_scalar = 1.0 / std::sqrt((double)S);
-        amp_norm2 = 1.0;
+        if (dalloc(phase, B * S) || dalloc(w, B * P) || dalloc(t, B * P) || dalloc(xg, S) || dalloc(yg, S) ||
+            dalloc(mono, (size_t)2 * c.n_monomials) || dalloc(coeff, (size_t)c_rows * P) ||
+            dalloc(cpartial, (size_t)B * std::max(c_nblocks, run_blocks) * P) ||
+            dalloc(cnorm, (size_t)B * ((P + C_RED_SPOTS - 1) / C_RED_SPOTS)) || dalloc(ext_amp, P) || dalloc(ext_r, B * P)) return HGS_ERR_DEVICE;
+        if (int e = alloc_partials((size_t)B, (size_t)B)) return e;
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }
@@ -826,10 +772,8 @@ template <typename R> struct Engine : EngineBase {
             r.ci = (float)std::sin(ang);
             r.pad0 = r.pad1 = 0;
         }
-        if (!run_rec) {
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&run_rec), (size_t)N * sizeof(CRunRec)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&run_ys), (size_t)H * sizeof(double)));
-        }
+        HIPCHK(run_rec.ensure((size_t)N));
+        HIPCHK(run_ys.ensure((size_t)H));
         if (int e_ = h2d(run_rec, rec.data(), rec.size() * sizeof(CRunRec))) return e_;
         if (int e_ = h2d(run_ys, ys_host.data(), (size_t)H * sizeof(double))) return e_;
         run_x0 = x0;
@@ -863,8 +807,8 @@ template <typename R> struct Engine : EngineBase {
     }
     int run_f2n(const CArgs<R>& a) {
         if (!run_nf || run_nf_chunks < run_chunks) {
-            if (run_nf) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(run_nf)); run_nf = nullptr; }
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&run_nf), (size_t)B * run_chunks * S * sizeof(Cx<float>)));
+            HIPCHK(run_nf.release(stream));
+            HIPCHK(run_nf.alloc((size_t)B * run_chunks * S));
             run_nf_chunks = run_chunks;
         }
         CRunArgs ra = run_args(a);
@@ -920,27 +864,22 @@ template <typename R> struct Engine : EngineBase {
                 };
                 sep_split1 = fill(t1, sk_kt1, sk_G1, tab.data(), tab.data() + t1);
                 sep_split2 = fill(t2, sk_kt2, sk_G2, tab.data() + 2 * t1, tab.data() + 2 * t1 + t2);
-                HIPCHK(hipMalloc(reinterpret_cast<void**>(&sk_tab), tab.size() * sizeof(int)));
+                HIPCHK(sk_tab.alloc(tab.size()));
                 if (int e_ = h2d(sk_tab, tab.data(), tab.size() * sizeof(int))) return e_;
             }
             sep_Np = up(N, CG_BM); sep_Hp = up(H, CG_BN); sep_Wp = up(W, CG_BN);
             sep_Wk = sk_kt1 * CG_BK;
             sep_Nk = sk_kt2 * CG_BK;
-            auto zalloc = [&](float2** p, size_t n) -> int {
-                HIPCHK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(float2)));
-                HIPCHK(hipMemsetAsync(*p, 0, n * sizeof(float2), stream));
-                return 0;
-            };
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&sep_c), c.size() * sizeof(double)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&sep_g), (size_t)(W + H) * sizeof(double)));
-            if (zalloc(&sep_ex, (size_t)sep_Nk * sep_Wp)) return HGS_ERR_DEVICE;       // [Nk][Wp]  (B of the f2n GEMM)
-            if (zalloc(&sep_exT, (size_t)sep_Wk * sep_Np)) return HGS_ERR_DEVICE;      // [Wk][Np]  (A of the n2f GEMM)
-            if (zalloc(&sep_ey, (size_t)N * H)) return HGS_ERR_DEVICE;
-            if (zalloc(&sep_nfT, (size_t)B * sep_Wk * sep_Hp)) return HGS_ERR_DEVICE;  // [B][Wk][Hp]
-            if (zalloc(&sep_b2, (size_t)B * sep_Nk * sep_Hp)) return HGS_ERR_DEVICE;   // [B][Nk][Hp]
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&sep_c1), (size_t)B * sk_tn1 * 2 * sep_split1 * sep_Np * sizeof(float2)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&sep_c2), (size_t)B * sep_split2 * H * W * sizeof(float2)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&sep_norm), (size_t)B * ((N + 255) / 256) * sizeof(double)));
+            HIPCHK(sep_c.alloc(c.size()));
+            HIPCHK(sep_g.alloc((size_t)(W + H)));
+            if (dalloc(sep_ex, (size_t)sep_Nk * sep_Wp)) return HGS_ERR_DEVICE;       // [Nk][Wp]  (B of the f2n GEMM)
+            if (dalloc(sep_exT, (size_t)sep_Wk * sep_Np)) return HGS_ERR_DEVICE;      // [Wk][Np]  (A of the n2f GEMM)
+            if (dalloc(sep_ey, (size_t)N * H)) return HGS_ERR_DEVICE;
+            if (dalloc(sep_nfT, (size_t)B * sep_Wk * sep_Hp)) return HGS_ERR_DEVICE;  // [B][Wk][Hp]
+            if (dalloc(sep_b2, (size_t)B * sep_Nk * sep_Hp)) return HGS_ERR_DEVICE;   // [B][Nk][Hp]
+            HIPCHK(sep_c1.alloc((size_t)B * sk_tn1 * 2 * sep_split1 * sep_Np));
+            HIPCHK(sep_c2.alloc((size_t)B * sep_split2 * H * W));
+            HIPCHK(sep_norm.alloc((size_t)B * ((N + 255) / 256)));
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cgemm_streamk<0>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)CG_LDS_BYTES));
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cgemm_streamk<1>),
@@ -982,11 +921,11 @@ template <typename R> struct Engine : EngineBase {
         const int N = cfg.n_spots, H = g.Sh, W = g.Sw;
         hipLaunchKernelGGL(sep_build_nft<R>, dim3((W + 31) / 32, (H + 31) / 32, B), dim3(32, 8), 0, stream, (const R*)phase,
                            has_amp ? (const R*)amp : (const R*)nullptr, has_kern ? (const R*)kern : (const R*)nullptr,
-                           (R)amp_scalar, H, W, reinterpret_cast<float*>(sep_nfT), sep_Hp, (size_t)sep_Wk * sep_Hp);
+                           (R)amp_scalar, H, W, reinterpret_cast<float*>(sep_nfT.get()), sep_Hp, (size_t)sep_Wk * sep_Hp);
         HIPCHK(hipGetLastError());
         const int t1 = sk_tm1 * sk_tn1;
-        if (int e = launch_cgemm(reinterpret_cast<const float*>(sep_exT), (size_t)sep_Wk * sep_Np,
-                                 reinterpret_cast<const float*>(sep_nfT), (size_t)sep_Wk * sep_Hp, nullptr, N, H, sk_kt1, sep_Np, sep_Hp,
+        if (int e = launch_cgemm(reinterpret_cast<const float*>(sep_exT.get()), (size_t)sep_Wk * sep_Np,
+                                 reinterpret_cast<const float*>(sep_nfT.get()), (size_t)sep_Wk * sep_Hp, nullptr, N, H, sk_kt1, sep_Np, sep_Hp,
                                  sk_tm1, sk_tn1, sep_split1, sk_tab, sk_G1, 0, (size_t)2 * sep_Wk * sep_Hp,
                                  (const float2*)sep_ey, H, sep_c1, sep_Np)) return e;
         const int nred = (N + 255) / 256;
@@ -1001,11 +940,11 @@ template <typename R> struct Engine : EngineBase {
     int sep_f2n(Cx<R>* nf_out) {
         const int N = cfg.n_spots, H = g.Sh, W = g.Sw;
         hipLaunchKernelGGL(sep_build_b2<R>, dim3((H + 255) / 256, N, B), dim3(256), 0, stream, (const Cx<R>*)ff,
-                           (const float2*)sep_ey, N, H, reinterpret_cast<float*>(sep_b2), sep_Hp, (size_t)sep_Nk * sep_Hp);
+                           (const float2*)sep_ey, N, H, reinterpret_cast<float*>(sep_b2.get()), sep_Hp, (size_t)sep_Nk * sep_Hp);
         HIPCHK(hipGetLastError());
         const int t1 = sk_tm1 * sk_tn1, t2 = sk_tm2 * sk_tn2;
-        if (int e = launch_cgemm(reinterpret_cast<const float*>(sep_b2), (size_t)sep_Nk * sep_Hp,
-                                 reinterpret_cast<const float*>(sep_ex), (size_t)sep_Nk * sep_Wp, sep_c2, H, W, sk_kt2, sep_Hp, sep_Wp,
+        if (int e = launch_cgemm(reinterpret_cast<const float*>(sep_b2.get()), (size_t)sep_Nk * sep_Hp,
+                                 reinterpret_cast<const float*>(sep_ex.get()), (size_t)sep_Nk * sep_Wp, sep_c2, H, W, sk_kt2, sep_Hp, sep_Wp,
                                  sk_tm2, sk_tn2, sep_split2, sk_tab + 2 * t1, sk_G2, (size_t)2 * sep_Nk * sep_Hp, 0)) return e;
         hipLaunchKernelGGL(sep_f2n_finish<R>, dim3((unsigned)((S + 255) / 256), B), dim3(256), 0, stream, (const float2*)sep_c2,
                            sep_split2, (const int*)(sk_tab + 2 * t1 + t2), sk_tm2, W, S,
@@ -1054,9 +993,8 @@ template <typename R> struct Engine : EngineBase {
             a.P = P; a.batch = B; a.ff = ff; a.pff = pff;
             hipLaunchKernelGGL(ew_store_phase<R>, dim3(ew_blocks, B), dim3(256), 0, stream, a);
             HIPCHK(hipGetLastError());
-            have_pff = true;
         }
-        farfield_valid = true;
+        state.farfield_materialised(store_pff != 0);
         return 0;
     }
     // the per-pixel compressed inverse, by polynomial degree (3: the monomial table; 0: any degree)
@@ -1069,48 +1007,39 @@ template <typename R> struct Engine : EngineBase {
         HIPCHK(hipGetLastError());
         return 0;
     }
-    int f2n_compressed() {
-        if (!ff || !farfield_valid) return fail(HGS_ERR_STATE, "no farfield to transform back");
+    // nf_out: null extracts the phase; else the complex nearfield goes there and the phase stays (f2n_complex)
+    int f2n_compressed(Cx<R>* nf_out = nullptr) {
+        if (!ff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "no farfield to transform back");
         int r = timed(HGS_K_COL_INV, [&]() -> int {
-            if (use_sep()) return sep_f2n(nullptr);
+            if (use_sep()) return sep_f2n(nf_out);
             CArgs<R> a = cargs();
+            a.nf_out = nf_out;
             if (use_run()) return run_f2n(a);
             return pix_f2n(a);
         });
-        farfield_valid = false;
+        state.farfield_consumed();
         return r;
     }
 
+    // wscale = 1: the launch alone; what it means for the weights is the caller's event (weights_written, scale_folded)
     int fill_wscale_one() {
-        hipLaunchKernelGGL(set_scalar<R>, dim3((B + 63) / 64), dim3(64), 0, stream, wscale, B, (R)1);
+        hipLaunchKernelGGL(set_scalar<R>, dim3((B + 63) / 64), dim3(64), 0, stream, wscale.get(), B, (R)1);
         HIPCHK(hipGetLastError());
-        w_pending = false;
-        w_unit = false;
+        return 0;
+    }
+    // the weights were written from outside the fused loop: whatever scale was pending is void
+    int weights_written() {
+        if (int e = fill_wscale_one()) return e;
+        state.weights_written();
         return 0;
     }
 
     // ---- lazily allocated farfield-sized buffers ----
-    int need_ff() {
-        if (!ff) { if (dalloc(&ff, B * P)) return HGS_ERR_DEVICE; }
-        if (!aff) { if (dalloc(&aff, B * P)) return HGS_ERR_DEVICE; }
-        return 0;
-    }
-    int need_aff() {
-        if (!aff) { if (dalloc(&aff, B * P)) return HGS_ERR_DEVICE; }
-        return 0;
-    }
-    int need_pff() {
-        if (!pff) { if (dalloc(&pff, B * P)) return HGS_ERR_DEVICE; }
-        return 0;
-    }
-    int need_staging() {
-        if (!staging) HIPCHK(hipMalloc(&staging, B * P * sizeof(C)));
-        return 0;
-    }
-    int need_zw() {
-        if (!zw) { if (dalloc(&zw, B * P)) return HGS_ERR_DEVICE; }
-        return 0;
-    }
+    int need_ff() { if (int e = need_zeroed(ff, B * P)) return e; return need_aff(); }
+    int need_aff() { return need_zeroed(aff, B * P); }
+    int need_pff() { return need_zeroed(pff, B * P); }
+    int need_staging() { return need(staging, B * P * sizeof(C)); }
+    int need_zw() { return need_zeroed(zw, B * P); }
 
     // ---- profiling wrapper ----
     template <typename F> int timed(int kind, F&& f) {
@@ -1151,7 +1080,7 @@ template <typename R> struct Engine : EngineBase {
         const size_t one = P * sizeof(E);
         if (nbytes != one * B && nbytes != one) return fail(HGS_ERR_ARG, "array size %zu does not match %zu x {1,%d}", nbytes, one, B);
         if (int e = need_staging()) return e;
-        E* st = reinterpret_cast<E*>(staging);
+        E* st = reinterpret_cast<E*>(staging.get());
         for (int b = 0; b < B; ++b) {
             const char* src = (const char*)host + (nbytes == one ? 0 : (size_t)b * one);
             HIPCHK(hipMemcpyAsync(st + (size_t)b * P, src, one, src_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
@@ -1167,21 +1096,20 @@ template <typename R> struct Engine : EngineBase {
         const size_t all = P * sizeof(E) * B;
         if (nbytes != all) return fail(HGS_ERR_ARG, "array size %zu does not match %zu", nbytes, all);
         if (int e = need_staging()) return e;
-        E* st = reinterpret_cast<E*>(staging);
+        E* st = reinterpret_cast<E*>(staging.get());
         dim3 grid((g.Ph + 31) / 32, (g.Pw + 31) / 32, B);
         hipLaunchKernelGGL((transpose_scale<E, R>), grid, dim3(32, 8), 0, stream, src, st, g.Pw, g.Ph, scale,
                            cfg.kind == 0 ? g.lane_T : 0, 0);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(dst, st, all, dst_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return 0;
+        return d2h(dst, st, all, dst_device);
     }
 
     int set_array(int which, const void* host, size_t nbytes, bool src_device) override {
-        if (which == HGS_PHASE || which == HGS_AMP || which == HGS_AMP_SCALAR || which == HGS_PROP_KERNEL) gh_state = -1;
+        const bool nearfield_input = which == HGS_PHASE || which == HGS_AMP || which == HGS_AMP_SCALAR || which == HGS_PROP_KERNEL;
+        if (nearfield_input) state.nearfield_upload_begins();
         if (which == HGS_PROP_KERNEL && nbytes == 0) {       // "no kernel" (Hologram.propagation_kernel = None / 0)
             has_kern = false;
-            farfield_valid = false;
+            state.nearfield_input_changed();
             return 0;
         }
         if (!host) return fail(HGS_ERR_ARG, "null source pointer");
@@ -1196,26 +1124,23 @@ template <typename R> struct Engine : EngineBase {
                 for (int b = 0; b < B; ++b)
                     HIPCHK(hipMemcpyAsync(phase + (size_t)b * S, (const char*)host + (nbytes == one ? 0 : b * one), one, kind, stream));
                 HIPCHK(hipStreamSynchronize(stream));
-                farfield_valid = false;
+                state.nearfield_input_changed();
                 return 0;
             }
             case HGS_AMP: {
                 if (nbytes != S * sizeof(R)) return fail(HGS_ERR_ARG, "amp: bad size %zu", nbytes);
-                if (!amp) HIPCHK(hipMalloc(reinterpret_cast<void**>(&amp), S * sizeof(R)));
+                HIPCHK(amp.ensure(S));
                 if (int e_ = h2d(amp, host, nbytes, src_device)) return e_;
                 has_amp = true;
                 double s = 0;
                 if (src_device) {         // ||amp||^2 on the device: per-block partials (double), folded here
                     const int nb = (int)std::min<size_t>((S + 255) / 256, 1024);
-                    double* part = nullptr;
-                    HIPCHK(hipMalloc(reinterpret_cast<void**>(&part), (size_t)nb * sizeof(double)));
-                    hipLaunchKernelGGL(ew_sumsq<R>, dim3(nb, 1), dim3(256), 0, stream, (const R*)amp, S, part);
-                    if (hipGetLastError() != hipSuccess) { hipFree(part); return fail(HGS_ERR_DEVICE, "amplitude norm launch failed"); }
+                    DevBuf<double> part;
+                    HIPCHK(part.alloc((size_t)nb));
+                    hipLaunchKernelGGL(ew_sumsq<R>, dim3(nb, 1), dim3(256), 0, stream, (const R*)amp, S, part.get());
+                    if (hipGetLastError() != hipSuccess) return fail(HGS_ERR_DEVICE, "amplitude norm launch failed");
                     std::vector<double> hp(nb);
-                    hipError_t e1 = hipMemcpyAsync(hp.data(), part, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream);
-                    hipError_t e2 = hipStreamSynchronize(stream);
-                    hipFree(part);
-                    if (e1 != hipSuccess || e2 != hipSuccess) return fail(HGS_ERR_DEVICE, "amplitude norm failed");
+                    if (d2h(hp.data(), part, (size_t)nb * sizeof(double))) return fail(HGS_ERR_DEVICE, "amplitude norm failed");
                     for (double v : hp) s += v;
                 } else {
                     const R* h = (const R*)host;
@@ -1223,7 +1148,7 @@ template <typename R> struct Engine : EngineBase {
                     for (size_t i = 0; i < S; ++i) { const double v = (double)h[i]; if (v == v) s += v * v; }
                 }
                 amp_norm2 = s;
-                farfield_valid = false;
+                state.nearfield_input_changed();
                 return 0;
             }
             case HGS_AMP_SCALAR: {
@@ -1231,35 +1156,34 @@ template <typename R> struct Engine : EngineBase {
                 amp_scalar = (double)*(const R*)host;
                 has_amp = false;
                 amp_norm2 = amp_scalar * amp_scalar * (double)S;
-                farfield_valid = false;
+                state.nearfield_input_changed();
                 return 0;
             }
             case HGS_PROP_KERNEL: {
                 if (nbytes != S * sizeof(R)) return fail(HGS_ERR_ARG, "propagation kernel: bad size %zu", nbytes);
-                if (!kern) HIPCHK(hipMalloc(reinterpret_cast<void**>(&kern), S * sizeof(R)));
+                HIPCHK(kern.ensure(S));
                 if (int e_ = h2d(kern, host, nbytes, src_device)) return e_;
                 has_kern = true;
-                farfield_valid = false;
+                state.nearfield_input_changed();
                 return 0;
             }
             case HGS_TARGET:
                 has_target = true;
-                sparse_dirty = true;
-                return upload_T<R>(t, host, nbytes, src_device);
+                state.target_written();
+                return upload_T<R>(t.get(), host, nbytes, src_device);
             case HGS_WEIGHTS: {
-                sparse_dirty = true;
-                int e = upload_T<R>(w, host, nbytes, src_device);
-                if (e) return e;
-                return fill_wscale_one();
+                state.weights_write_begins();
+                if (int e = upload_T<R>(w.get(), host, nbytes, src_device)) return e;
+                return weights_written();
             }
             case HGS_PHASE_FF: {
                 if (int e = need_pff()) return e;
-                have_pff = true;
-                return upload_T<R>(pff, host, nbytes, src_device);
+                state.phase_ff_stored();
+                return upload_T<R>(pff.get(), host, nbytes, src_device);
             }
             case HGS_ZERO_WEIGHTS: {
                 if (int e = need_zw()) return e;
-                return upload_T<C>(zw, host, nbytes, src_device);
+                return upload_T<C>(zw.get(), host, nbytes, src_device);
             }
             case HGS_XGRID:
             case HGS_YGRID: {
@@ -1267,7 +1191,7 @@ template <typename R> struct Engine : EngineBase {
                 if (nbytes != S * sizeof(R)) return fail(HGS_ERR_ARG, "grid: bad size %zu", nbytes);
                 if (int e_ = h2d(which == HGS_XGRID ? xg : yg, host, nbytes)) return e_;
                 has_grid[which == HGS_XGRID ? 0 : 1] = true;
-                farfield_valid = false;
+                state.geometry_changed();
                 {   // product grid?  x depends on the column only, y on the row only
                     const R* h = (const R*)host;
                     const int H = g.Sh, W = g.Sw;
@@ -1297,7 +1221,7 @@ template <typename R> struct Engine : EngineBase {
                 mono_host.assign(h, h + 2 * cfg.n_monomials);
                 if (int e_ = h2d(mono, host, nbytes)) return e_;
                 has_mono = true;
-                farfield_valid = false;
+                state.geometry_changed();
                 return pack_coeff();
             }
             case HGS_SPOT_COEFF: {
@@ -1306,7 +1230,7 @@ template <typename R> struct Engine : EngineBase {
                 const R* h = (const R*)host;
                 coeff_host.assign(h, h + (size_t)cfg.n_monomials * cfg.n_spots);
                 has_coeff = true;
-                farfield_valid = false;
+                state.geometry_changed();
                 return pack_coeff();
             }
             case HGS_SPOT_INDEX: {
@@ -1327,8 +1251,7 @@ template <typename R> struct Engine : EngineBase {
                 if (cfg.kind == 1 && which == HGS_SPOT_AMP) return fail(HGS_ERR_ARG, "compressed targets are set with HGS_TARGET");
                 if (cfg.n_spots <= 0) return fail(HGS_ERR_STATE, "engine was created with n_spots = 0");
                 if (nbytes != (size_t)cfg.n_spots * sizeof(double)) return fail(HGS_ERR_ARG, "spot amplitudes: bad size");
-                if (int e_ = h2d(which == HGS_SPOT_AMP ? spot_amp : ext_amp, host, nbytes, src_device)) return e_;
-                return 0;
+                return h2d(which == HGS_SPOT_AMP ? spot_amp : ext_amp, host, nbytes, src_device);
             }
         }
         return fail(HGS_ERR_ARG, "unknown array selector %d", which);
@@ -1350,82 +1273,66 @@ template <typename R> struct Engine : EngineBase {
             else HIPCHK(hipMemcpyPeerAsync(phase + (size_t)b * S, cfg.device, from, src.device, S * sizeof(R), stream));
         }
         HIPCHK(hipStreamSynchronize(stream));
-        farfield_valid = false;
-        gh_state = -1;
+        state.nearfield_input_changed();
         return 0;
     }
 
     int normalize_weights_now() {
         // fold the pending 1/||w|| into the stored weights (general path keeps them normalised)
-        if (!w_pending) return 0;
-        w_outside_scan = true;        // (a non-finite scale -- all weights zero -- turns the zeros of every column into NaN)
-        hipLaunchKernelGGL(scale_weights_kernel<R>, dim3(ew_blocks, B), dim3(256), 0, stream, w, (const R*)wscale, P);
+        if (!state.w_pending()) return 0;
+        hipLaunchKernelGGL(scale_weights_kernel<R>, dim3(ew_blocks, B), dim3(256), 0, stream, w.get(), (const R*)wscale, P);
         HIPCHK(hipGetLastError());
-        return fill_wscale_one();
+        if (int e = fill_wscale_one()) return e;
+        state.scale_folded();
+        return 0;
     }
     int get_array(int which, void* dst, size_t nbytes, bool dst_device) override {
         if (!dst) return fail(HGS_ERR_ARG, "null destination pointer");
         switch (which) {
-            case HGS_PHASE: {
+            case HGS_PHASE:
                 if (nbytes != S * sizeof(R) * B) return fail(HGS_ERR_ARG, "phase: bad size %zu", nbytes);
-                HIPCHK(hipMemcpyAsync(dst, phase, nbytes, dst_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                return 0;
-            }
-            case HGS_PHASE_PREV: {
-                if (!phase_prev || !have_prev) return fail(HGS_ERR_STATE, "no previous phase is held (HGS_OPT_KEEP_PREV_PHASE, one-iteration fused calls)");
+                return d2h(dst, phase, nbytes, dst_device);
+            case HGS_PHASE_PREV:
+                if (!phase_prev || !state.have_prev()) return fail(HGS_ERR_STATE, "no previous phase is held (HGS_OPT_KEEP_PREV_PHASE, one-iteration fused calls)");
                 if (nbytes != S * sizeof(R) * B) return fail(HGS_ERR_ARG, "previous phase: bad size %zu", nbytes);
-                HIPCHK(hipMemcpyAsync(dst, phase_prev, nbytes, dst_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                return 0;
-            }
-            case HGS_CG_GRAD: {
-                if (!cg_grad || !cg_have_grad) return fail(HGS_ERR_STATE, "no gradient is held (hgs_cg_iterate with keep_grad has not run)");
+                return d2h(dst, phase_prev, nbytes, dst_device);
+            case HGS_CG_GRAD:
+                if (!cg_grad || !state.cg_have_grad()) return fail(HGS_ERR_STATE, "no gradient is held (hgs_cg_iterate with keep_grad has not run)");
                 if (nbytes != S * sizeof(R)) return fail(HGS_ERR_ARG, "gradient: bad size %zu", nbytes);
-                HIPCHK(hipMemcpyAsync(dst, cg_grad, nbytes, dst_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                return 0;
-            }
-            case HGS_VORTICES: {
+                return d2h(dst, cg_grad, nbytes, dst_device);
+            case HGS_VORTICES:
                 if (vx_n < 0) return fail(HGS_ERR_STATE, "no vortex list is held (hgs_remove_vortices has not run)");
                 if (nbytes != (size_t)vx_n * 3 * sizeof(int32_t)) return fail(HGS_ERR_ARG, "vortices: bad size %zu (the last call found %d)", nbytes, vx_n);
                 if (vx_n == 0) return 0;
-                HIPCHK(hipMemcpyAsync(dst, vx_list, nbytes, dst_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                return 0;
-            }
-            case HGS_TARGET: return download_T<R>(t, dst, nbytes, dst_device, nullptr);
-            case HGS_WEIGHTS: return download_T<R>(w, dst, nbytes, dst_device, w_pending ? wscale : nullptr);
+                return d2h(dst, vx_list, nbytes, dst_device);
+            case HGS_TARGET: return download_T<R>(t.get(), dst, nbytes, dst_device, nullptr);
+            case HGS_WEIGHTS: return download_T<R>(w.get(), dst, nbytes, dst_device, state.w_pending() ? wscale.get() : nullptr);
             case HGS_PHASE_FF:
-                if (!pff || !have_pff) return fail(HGS_ERR_STATE, "phase_ff has not been computed");
-                return download_T<R>(pff, dst, nbytes, dst_device, nullptr);
+                if (!pff || !state.have_pff()) return fail(HGS_ERR_STATE, "phase_ff has not been computed");
+                return download_T<R>(pff.get(), dst, nbytes, dst_device, nullptr);
             case HGS_FARFIELD:
-                if (!ff || !farfield_valid) return fail(HGS_ERR_STATE, "farfield is not materialised (call hgs_nearfield2farfield)");
-                return download_T<C>(ff, dst, nbytes, dst_device, nullptr);
+                if (!ff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "farfield is not materialised (call hgs_nearfield2farfield)");
+                return download_T<C>(ff.get(), dst, nbytes, dst_device, nullptr);
             case HGS_AMP_FF:
-                if (!aff || !farfield_valid) return fail(HGS_ERR_STATE, "amp_ff is not materialised (call hgs_nearfield2farfield)");
-                return download_T<R>(aff, dst, nbytes, dst_device, nullptr);
+                if (!aff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "amp_ff is not materialised (call hgs_nearfield2farfield)");
+                return download_T<R>(aff.get(), dst, nbytes, dst_device, nullptr);
             case HGS_ZERO_WEIGHTS:
                 if (!zw) return fail(HGS_ERR_STATE, "zero_weights not allocated");
-                return download_T<C>(zw, dst, nbytes, dst_device, nullptr);
+                return download_T<C>(zw.get(), dst, nbytes, dst_device, nullptr);
         }
         return fail(HGS_ERR_ARG, "array selector %d cannot be read back", which);
     }
 
     int reset_weights() override {
-        sparse_dirty = true;
-        hipLaunchKernelGGL(reset_weights_kernel<R>, dim3(ew_blocks * B), dim3(256), 0, stream, w, (const R*)t, zw, B * P);
+        state.weights_write_begins();
+        hipLaunchKernelGGL(reset_weights_kernel<R>, dim3(ew_blocks * B), dim3(256), 0, stream, w.get(), (const R*)t, zw.get(), B * P);
         HIPCHK(hipGetLastError());
-        return fill_wscale_one();
+        return weights_written();
     }
     // Hologram.reset (:442-478): weights from the target, phase_ff / farfield / amp_ff back to "None"
     int reset_state() override {
-        have_pff = false;
-        have_prev = false;
-        farfield_valid = false;
-        gh_state = -1;          // (a kept G is the un-extracted phasor of the last body: a reset hologram starts from its phase, like a new one)
-        cg_t = 0;               // Adam starts over (hgs_cg_iterate zeroes the moments at step 0) and no gradient is held
-        cg_have_grad = false;
+        state.reset_state();
+        cg_t = 0;               // Adam starts over (hgs_cg_iterate zeroes the moments at step 0)
         return reset_weights();
     }
     // n values at listed pixels, `0` everywhere else (SpotHologram targets: n_spots numbers instead of P)
@@ -1456,10 +1363,10 @@ template <typename R> struct Engine : EngineBase {
         HIPCHK(hipMemsetAsync(dst, 0, (size_t)B * P * sizeof(R), stream));
         const int m = (int)pos.size();
         if (m > 0) {
-            uint32_t* dpos = nullptr;
-            R* dval = nullptr;
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&dpos), (size_t)m * sizeof(uint32_t)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&dval), (size_t)m * sizeof(R)));
+            DevBuf<uint32_t> dpos;
+            DevBuf<R> dval;
+            HIPCHK(dpos.alloc((size_t)m));
+            HIPCHK(dval.alloc((size_t)m));
             hipError_t e1 = hipMemcpyAsync(dpos, pos.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
             hipError_t e2 = hipMemcpyAsync(dval, val.data(), (size_t)m * sizeof(R), hipMemcpyHostToDevice, stream);
             if (e1 == hipSuccess && e2 == hipSuccess) {
@@ -1467,16 +1374,13 @@ template <typename R> struct Engine : EngineBase {
                                    (const R*)dval, m, P);
                 e1 = hipGetLastError();
             }
-            hipStreamSynchronize(stream);
-            hipFree(dpos);
-            hipFree(dval);
+            hipStreamSynchronize(stream);       // (pos / val and the two device lists go out of scope)
             if (e1 != hipSuccess || e2 != hipSuccess) return fail(HGS_ERR_DEVICE, "sparse upload failed");
         } else {
             HIPCHK(hipStreamSynchronize(stream));
         }
-        sparse_dirty = true;
-        if (which == HGS_TARGET) { has_target = true; return 0; }
-        return fill_wscale_one();
+        if (which == HGS_TARGET) { has_target = true; state.target_written(); return 0; }
+        return weights_written();
     }
 
     // ---- operator launches ----
@@ -1499,27 +1403,27 @@ template <typename R> struct Engine : EngineBase {
     // mode: row_kernel MODE (3 = MODE 2 that also writes the phase; float32 only)
     // cp: the column pass this launch closes (the partials it folds, the join of a single-pass MRAF body), or null
     int run_row(int mode, bool finalize, int load_sparse = 0, int store_sparse = 0, const ColumnPlan* cp = nullptr) {
-        gh_state = -1;
+        state.row_launch_begins();
         int r_ = run_row_impl(mode, finalize, load_sparse, store_sparse, cp);
-        if (r_ == 0 && mode != 1) gh_state = store_sparse;      // gh holds G of the columns this launch stored
+        if (r_ == 0) state.row_stored_g(mode, store_sparse);      // gh holds G of the columns this launch stored
         return r_;
     }
     // (fused loops only; p = the plan of the call's first iteration)
     int keep_prev_phase(const Plan& p, int n) {
         if (!opt_prev_phase) return 0;
-        if (n != 1) { have_prev = false; return 0; }      // the phases in between are never materialised
+        if (n != 1) { state.prev_phase_dropped(); return 0; }      // the phases in between are never materialised
         if (p.use_fixed) return 0;                          // phase_ff is not rewritten: what is held stays what describes it
-        if (!phase_prev) { if (dalloc(&phase_prev, (size_t)B * S)) return HGS_ERR_DEVICE; }
+        if (need_zeroed(phase_prev, (size_t)B * S)) return HGS_ERR_DEVICE;
         HIPCHK(hipMemcpyAsync(phase_prev, phase, (size_t)B * S * sizeof(R), hipMemcpyDeviceToDevice, stream));
-        have_prev = true;
+        state.prev_phase_kept();
         return 0;
     }
-    bool gh_holds(int need) const { return tun.keep_g && (gh_state == need || gh_state == 0 || (gh_state == 2 && need == 1 && dil_valid)); }
+    bool gh_holds(int need) const { return state.gh_holds(need, tun.keep_g != 0); }
     int run_row_impl(int mode, bool finalize, int load_sparse, int store_sparse, const ColumnPlan* cp) {
         return timed(HGS_K_ROW, [&]() -> int {
             RowArgs<R> a = row_args(finalize, cp ? cp->wpartial_n : 0);
-            a.load_mask = load_sparse == 1 ? lane_mask : load_sparse == 2 ? lane_mask_d : nullptr;
-            a.store_mask = store_sparse == 1 ? lane_mask : store_sparse == 2 ? lane_mask_d : nullptr;
+            a.load_mask = load_sparse == 1 ? active.mask.get() : load_sparse == 2 ? dilated.mask.get() : nullptr;
+            a.store_mask = store_sparse == 1 ? active.mask.get() : store_sparse == 2 ? dilated.mask.get() : nullptr;
             // one extra (row-less) block folds the weight-norm partials when asked to
             // dense fp32 launches between iterations at 4096: workgroups walk several rows, next row prefetched into LDS
             int blocks = row_blocks;
@@ -1535,7 +1439,7 @@ template <typename R> struct Engine : EngineBase {
                 a.prefetch = 0;
                 a.n_row_blocks = blocks = row_blocks;
                 a.gh2 = gh2;
-                a.gh2_mask = cp->gh2_mask ? lane_mask_noise : nullptr;
+                a.gh2_mask = cp->gh2_mask ? lane_mask_noise.get() : nullptr;
                 LCHK(launch_row_split(g.Pw, mode, dim3(blocks, B), stream, a));
                 return 0;
             }
@@ -1545,25 +1449,14 @@ template <typename R> struct Engine : EngineBase {
     }
     // active columns dilated by the offsets [lo, hi] of the spot integration window
     int refresh_dilated(int lo, int hi) {
-        if (dil_valid && lo == dil_lo && hi == dil_hi) return 0;
-        if (gh_state == 2) gh_state = -1;
-        if (!col_active_d) {
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&col_active_d), (size_t)B * g.Pw));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&col_list_d), (size_t)B * g.Pw * sizeof(int)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&n_active_d_dev), (size_t)B * sizeof(int)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&lane_mask_d), (size_t)B * (g.Pw / 16) * sizeof(unsigned short)));
-        }
+        if (state.dilation_is(lo, hi)) return 0;
+        state.dilation_rebuild_begins();
+        HIPCHK(col_active_d.ensure((size_t)B * g.Pw));
         hipLaunchKernelGGL(dilate_active_cols, dim3((g.Pw + 255) / 256, B), dim3(256), 0, stream,
-                           (const unsigned char*)col_active, g.Pw, lo, hi, col_active_d);
+                           (const unsigned char*)col_active, g.Pw, lo, hi, col_active_d.get());
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(compact_active_cols, dim3(B), dim3(256), 0, stream, (const unsigned char*)col_active_d, g.Pw,
-                           col_list_d, n_active_d_dev, lane_mask_d);
-        HIPCHK(hipGetLastError());
-        std::vector<int> h(B);
-        HIPCHK(hipMemcpyAsync(h.data(), n_active_d_dev, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        n_active_d_max = *std::max_element(h.begin(), h.end());
-        dil_lo = lo; dil_hi = hi; dil_valid = true;
+        if (int e = dilated.build(col_active_d, 0xff, B, g.Pw, stream)) return e;
+        state.dilation_rebuilt(lo, hi);
         return 0;
     }
     // what plan_column_pass() reads, as far as it does not depend on the iteration: geometry, switches, the last column scan
@@ -1572,26 +1465,21 @@ template <typename R> struct Engine : EngineBase {
         f.elem = (int)sizeof(R);
         f.Ph = g.Ph; f.Pw = g.Pw; f.B = B; f.n_cu = n_cu; f.col_blocks = col_blocks; f.tile_blocks = tile_blocks; f.r0 = g.r0; f.Sh = g.Sh;
         f.stat_groups = stat_ctx ? stat_ctx->groups : 0;
-        f.w_unit = w_unit;
-        f.sparse_tiles = sparse_tiles; f.sparse_dirty = sparse_dirty; f.w_outside_scan = w_outside_scan;
-        f.n_active_min = n_active_min; f.n_active_max = n_active_max; f.n_noise_max = n_noise_max; f.n_signal_max = n_signal_max;
+        f.w_unit = state.w_unit();
+        f.sparse_tiles = sparse_tiles; f.sparse_dirty = state.sparse_dirty(); f.w_outside_scan = state.w_outside_scan();
+        f.n_active_min = active.n_min; f.n_active_max = active.n_max; f.n_noise_max = noise.n_max; f.n_signal_max = signal.n_max;
         f.tun = tun;
         return f;
     }
     bool tile_geometry_ok() const { return hgs::tile_geometry_ok(base_facts()); }
     // (re)build the active-column list when weights or target changed since the last scan
     int refresh_sparse() {
-        if (!sparse_dirty) return 0;
-        if (gh_state > 0) gh_state = -1;       // (a G stored on the old column lists; one of every column stays good)
-        if (!col_active) {
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&col_active), (size_t)B * g.Pw));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&sig_rows), (size_t)B * g.Pw * sizeof(unsigned short)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&col_list), (size_t)B * g.Pw * sizeof(int)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&n_active_dev), (size_t)B * sizeof(int)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&lane_mask), (size_t)B * (g.Pw / 16) * sizeof(unsigned short)));
-        }
+        if (!state.sparse_dirty()) return 0;
+        state.scan_started();
+        HIPCHK(col_active.ensure((size_t)B * g.Pw));
+        HIPCHK(sig_rows.ensure((size_t)B * g.Pw));
         hipLaunchKernelGGL(scan_active_cols<R>, dim3(g.Pw, B), dim3(256), 0, stream, (const R*)w, (const R*)t, g.Ph, g.Pw,
-                           col_active, g.lane_T > 0 ? sig_rows : (unsigned short*)nullptr);
+                           col_active.get(), g.lane_T > 0 ? sig_rows.get() : (unsigned short*)nullptr);
         HIPCHK(hipGetLastError());
         // Where the tile-resident kernel can run the column pass and the active columns fill their 4-column tiles at least
         // half (images, MRAF noise boxes -- not spot arrays, whose columns sit alone in their tiles), the active set is
@@ -1600,8 +1488,7 @@ template <typename R> struct Engine : EngineBase {
         sparse_tiles = false;
         if (tile_geometry_ok() && tun.tile_list) {
             std::vector<unsigned char> act((size_t)B * g.Pw);
-            HIPCHK(hipMemcpyAsync(act.data(), col_active, act.size(), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
+            if (int e = d2h(act.data(), col_active, act.size())) return e;
             bool dense = true;
             for (int b = 0; b < B && dense; ++b) {
                 int n_col = 0, n_tile = 0;
@@ -1618,47 +1505,24 @@ template <typename R> struct Engine : EngineBase {
                     const unsigned char on = (act[c] | act[c + 1] | act[c + 2] | act[c + 3]) ? 1 : 0;
                     for (int k = 0; k < 4; ++k) act[c + k] |= on;          // (bits 1, 2 of scan_active_cols stay per column)
                 }
-                HIPCHK(hipMemcpyAsync(col_active, act.data(), act.size(), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipStreamSynchronize(stream));      // (act goes out of scope)
+                if (int e = h2d(col_active, act.data(), act.size())) return e;
                 sparse_tiles = true;
             }
         }
-        hipLaunchKernelGGL(compact_active_cols, dim3(B), dim3(256), 0, stream, (const unsigned char*)col_active, g.Pw,
-                           col_list, n_active_dev, lane_mask);
-        HIPCHK(hipGetLastError());
-        if (!lane_mask_noise) HIPCHK(hipMalloc(reinterpret_cast<void**>(&lane_mask_noise), (size_t)B * (g.Pw / 16) * sizeof(unsigned short)));
+        if (int e = active.build(col_active, 0xff, B, g.Pw, stream)) return e;
+        HIPCHK(lane_mask_noise.ensure((size_t)B * (g.Pw / 16)));
         hipLaunchKernelGGL(flag_lane_mask, dim3((g.Pw / 16 + 255) / 256, B), dim3(256), 0, stream, (const unsigned char*)col_active,
-                           g.Pw, 4, lane_mask_noise);
+                           g.Pw, 4, lane_mask_noise.get());
         HIPCHK(hipGetLastError());
-        std::vector<int> h(B);
-        HIPCHK(hipMemcpyAsync(h.data(), n_active_dev, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        n_active_max = *std::max_element(h.begin(), h.end());
-        n_active_min = *std::min_element(h.begin(), h.end());
-        sparse_dirty = false;
-        w_outside_scan = false;
-        dil_valid = false;
-        noise_valid = false;
-        signal_valid = false;
+        state.scan_finished();
         return 0;
     }
     // the columns that hold a finite non-zero target as a list (the per-column pre-pass of the single-inverse MRAF update)
     int refresh_signal() {
         if (int e = refresh_sparse()) return e;
-        if (signal_valid) return 0;
-        if (!col_list_signal) {
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&col_list_signal), (size_t)B * g.Pw * sizeof(int)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&n_signal_dev), (size_t)B * sizeof(int)));
-        }
-        if (!lane_mask_tmp) HIPCHK(hipMalloc(reinterpret_cast<void**>(&lane_mask_tmp), (size_t)B * (g.Pw / 16) * sizeof(unsigned short)));
-        hipLaunchKernelGGL(compact_active_cols, dim3(B), dim3(256), 0, stream, (const unsigned char*)col_active, g.Pw,
-                           col_list_signal, n_signal_dev, lane_mask_tmp, 2);
-        HIPCHK(hipGetLastError());
-        std::vector<int> h(B);
-        HIPCHK(hipMemcpyAsync(h.data(), n_signal_dev, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        n_signal_max = *std::max_element(h.begin(), h.end());
-        signal_valid = true;
+        if (state.signal_valid()) return 0;
+        if (int e = signal.build(col_active, 2, B, g.Pw, stream)) return e;
+        state.signal_list_rebuilt();
         return 0;
     }
     // per-column single-pass MRAF: the columns that hold a NaN target as a list (the buffer of the noise part is zeroed by the
@@ -1666,21 +1530,10 @@ template <typename R> struct Engine : EngineBase {
     // as zero, also after the target moved)
     int refresh_noise() {
         if (int e = refresh_sparse()) return e;
-        if (noise_valid) return 0;
-        if (!col_list_noise) {
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&col_list_noise), (size_t)B * g.Pw * sizeof(int)));
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&n_noise_dev), (size_t)B * sizeof(int)));
-        }
-        if (!lane_mask_tmp) HIPCHK(hipMalloc(reinterpret_cast<void**>(&lane_mask_tmp), (size_t)B * (g.Pw / 16) * sizeof(unsigned short)));
-        ffb_zeroed = false;
-        hipLaunchKernelGGL(compact_active_cols, dim3(B), dim3(256), 0, stream, (const unsigned char*)col_active, g.Pw,
-                           col_list_noise, n_noise_dev, lane_mask_tmp, 4);
-        HIPCHK(hipGetLastError());
-        std::vector<int> h(B);
-        HIPCHK(hipMemcpyAsync(h.data(), n_noise_dev, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        n_noise_max = *std::max_element(h.begin(), h.end());
-        noise_valid = true;
+        if (state.noise_valid()) return 0;
+        state.noise_list_rebuild_begins();
+        if (int e = noise.build(col_active, 4, B, g.Pw, stream)) return e;
+        state.noise_list_rebuilt();
         return 0;
     }
     ColArgs<R> col_args() {
@@ -1708,7 +1561,7 @@ template <typename R> struct Engine : EngineBase {
         if (int e = need_ff()) return e;
         if (store_pff) { if (int e = need_pff()) return e; }
         // (a fused loop that ended on its dense row launch left G of every column behind: the transform starts with its column pass)
-        if (!(tun.keep_g && gh_state == 0)) { if (int e = run_row(0, false)) return e; }
+        if (!gh_holds(0)) { if (int e = run_row(0, false)) return e; }
         int r = timed(HGS_K_COL_FWD, [&]() -> int {
             ColArgs<R> a = col_args();
             a.store_pff = store_pff;
@@ -1717,8 +1570,7 @@ template <typename R> struct Engine : EngineBase {
         });
         if (r) return r;
         if (int e = reduce(fpartial, col_blocks, sums + 0 * B)) return e;
-        if (store_pff) have_pff = true;
-        farfield_valid = true;
+        state.farfield_materialised(store_pff != 0);
         return 0;
     }
 
@@ -1726,41 +1578,29 @@ template <typename R> struct Engine : EngineBase {
         RoctxRange range(opt_roctx, "hgs_farfield2nearfield");
         if (cfg.kind == 1) return f2n_compressed();
         if (general) return f2n_general(false);
-        if (!ff || !farfield_valid) return fail(HGS_ERR_STATE, "no farfield to transform back");
+        if (!ff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "no farfield to transform back");
+        if (int e = inverse_columns()) return e;
+        return run_row(1, false);
+    }
+    // the column half of the inverse transform, every column: ff -> gh
+    int inverse_columns() {
         int r = timed(HGS_K_COL_INV, [&]() -> int {
-            gh_state = -1;
+            state.column_pass_begins();
             LCHK(launch_col<R>(g.Ph, C_LOAD | C_INV, dim3(col_blocks, B), stream, col_args()));
             return 0;
         });
-        if (r) return r;
-        farfield_valid = false;  // farfield now holds the constrained field, phase moves on
-        return run_row(1, false);
+        if (r == 0) state.farfield_consumed();  // farfield now holds the constrained field, phase moves on
+        return r;
     }
 
     // Hologram._farfield2nearfield(extract=False) (:1058-1073): the complex nearfield over the SLM,
     // kept on the device for MultiplaneHologram's weighted sum
     int f2n_complex() override {
-        if (!ff || !farfield_valid) return fail(HGS_ERR_STATE, "no farfield to transform back");
-        if (!nfbuf) { if (dalloc(&nfbuf, B * S)) return HGS_ERR_DEVICE; }
+        if (!ff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "no farfield to transform back");
+        if (need_zeroed(nfbuf, B * S)) return HGS_ERR_DEVICE;
         if (general) return f2n_general(true);
-        if (cfg.kind == 1) {
-            int r = timed(HGS_K_COL_INV, [&]() -> int {
-                if (use_sep()) return sep_f2n(nfbuf);
-                CArgs<R> a = cargs();
-                a.nf_out = nfbuf;
-                if (use_run()) return run_f2n(a);
-                return pix_f2n(a);
-            });
-            farfield_valid = false;
-            return r;
-        }
-        int r = timed(HGS_K_COL_INV, [&]() -> int {
-            gh_state = -1;
-            LCHK(launch_col<R>(g.Ph, C_LOAD | C_INV, dim3(col_blocks, B), stream, col_args()));
-            return 0;
-        });
-        if (r) return r;
-        farfield_valid = false;
+        if (cfg.kind == 1) return f2n_compressed(nfbuf);
+        if (int e = inverse_columns()) return e;
         return timed(HGS_K_ROW, [&]() -> int {
             RowArgs<R> a = row_args(false);
             a.nf_out = nfbuf;
@@ -1784,19 +1624,20 @@ template <typename R> struct Engine : EngineBase {
         if (!has_target) return fail(HGS_ERR_STATE, "target has not been set");
         // (each buffer on its own pointer: a call that failed half way allocates the rest next time.  The moments are
         //  zeroed by whoever starts Adam: a restart, or -- cg_t == 0 -- a first call and the first one after hgs_reset)
-        if (!cg_m) { if (dalloc(&cg_m, S)) return HGS_ERR_DEVICE; cg_t = 0; }
-        if (!cg_v) { if (dalloc(&cg_v, S)) return HGS_ERR_DEVICE; cg_t = 0; }
-        if (!cg_partial) { if (dalloc(&cg_partial, (size_t)ew_blocks)) return HGS_ERR_DEVICE; }
+        if (!cg_m) { if (dalloc(cg_m, S)) return HGS_ERR_DEVICE; cg_t = 0; }
+        if (!cg_v) { if (dalloc(cg_v, S)) return HGS_ERR_DEVICE; cg_t = 0; }
+        if (need_zeroed(cg_partial, (size_t)ew_blocks)) return HGS_ERR_DEVICE;
         if (p->restart) cg_t = 0;
         if (cg_t == 0) {
             HIPCHK(hipMemsetAsync(cg_m, 0, S * sizeof(R), stream));
             HIPCHK(hipMemsetAsync(cg_v, 0, S * sizeof(R), stream));
         }
-        if (p->keep_grad && !cg_grad) { if (dalloc(&cg_grad, S)) return HGS_ERR_DEVICE; }
+        if (p->keep_grad && !cg_grad) { if (dalloc(cg_grad, S)) return HGS_ERR_DEVICE; }
         if (n == 0) return 0;
         if (cg_loss_cap < n) {
-            if (cg_loss) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipFree(cg_loss)); cg_loss = nullptr; cg_loss_cap = 0; }
-            if (dalloc(&cg_loss, (size_t)n)) return HGS_ERR_DEVICE;
+            cg_loss_cap = 0;
+            HIPCHK(cg_loss.release(stream));
+            if (dalloc(cg_loss, (size_t)n)) return HGS_ERR_DEVICE;
             cg_loss_cap = n;
         }
         for (int it = 0; it < n; ++it) {
@@ -1808,7 +1649,7 @@ template <typename R> struct Engine : EngineBase {
                 return reduce(cg_partial, ew_blocks, cg_loss + it);
             });
             if (r) return r;
-            // (ff holds the seed now; farfield_valid stays set for the inverse, which clears it -- and gh_state with it)
+            // (ff holds the seed now; the farfield stays valid for the inverse, which consumes it -- and drops G)
             if (int e = f2n_complex()) return e;
             ++cg_t;
             r = timed(HGS_K_CG_ADAM, [&]() -> int {
@@ -1823,12 +1664,11 @@ template <typename R> struct Engine : EngineBase {
                 return 0;
             });
             if (r) return r;
-            if (p->keep_grad) cg_have_grad = true;
+            if (p->keep_grad) state.cg_gradient_stored();
         }
-        have_prev = false;      // (HGS_PHASE_PREV described the phase a fused body started from: it is no longer the previous one)
+        state.prev_phase_dropped();      // (HGS_PHASE_PREV described the phase a fused body started from: it is no longer the previous one)
         if (loss_out) {
-            HIPCHK(hipMemcpyAsync(loss_out, cg_loss, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
+            if (int e = d2h(loss_out, cg_loss, (size_t)n * sizeof(double))) return e;
             for (int it = 0; it < n; ++it) loss_out[it] /= (double)P;      // mean reduction
         }
         return 0;
@@ -1842,11 +1682,11 @@ template <typename R> struct Engine : EngineBase {
         RoctxRange range(opt_roctx, "hgs_remove_vortices");
         if (cfg.kind != 0) return fail(HGS_ERR_UNSUPPORTED, "hgs_remove_vortices: padded-grid holograms only (engine kind 0)");
         if (B != 1) return fail(HGS_ERR_UNSUPPORTED, "hgs_remove_vortices: one hologram per engine (batch is %d)", B);
-        if (!pff || !have_pff) return fail(HGS_ERR_STATE, "phase_ff has not been computed");
+        if (!pff || !state.have_pff()) return fail(HGS_ERR_STATE, "phase_ff has not been computed");
         if (!has_target) return fail(HGS_ERR_STATE, "target has not been set");
         const unsigned blocks = vortex_find_blocks(P);
-        if (!vx_counts) { if (dalloc(&vx_counts, (size_t)blocks)) return HGS_ERR_DEVICE; }
-        if (!vx_count) { if (dalloc(&vx_count, (size_t)1)) return HGS_ERR_DEVICE; }
+        if (need_zeroed(vx_counts, (size_t)blocks)) return HGS_ERR_DEVICE;
+        if (need_zeroed(vx_count, (size_t)1)) return HGS_ERR_DEVICE;
         vx_n = -1;
         VortexFindArgs<R> f{};
         f.pff = pff; f.t = t; f.counts = vx_counts; f.list = vx_list; f.cap = vx_cap; f.pass = 0; f.P = P;
@@ -1858,13 +1698,13 @@ template <typename R> struct Engine : EngineBase {
             return 0;
         });
         if (r) return r;
-        HIPCHK(hipMemcpyAsync(&n, vx_count, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
+        if (int e = d2h(&n, vx_count, sizeof(int32_t))) return e;
         if (n > 0) {
             if ((unsigned)n > vx_cap) {
-                if (vx_list) { HIPCHK(hipFree(vx_list)); vx_list = nullptr; vx_cap = 0; }
+                vx_cap = 0;
+                HIPCHK(vx_list.release(stream));
                 const size_t cap = std::max<size_t>(1024, (size_t)n + (size_t)n / 2);      // (a cleaned phase holds fewer the next time)
-                if (dalloc(&vx_list, 3 * cap)) return HGS_ERR_DEVICE;
+                if (dalloc(vx_list, 3 * cap)) return HGS_ERR_DEVICE;
                 vx_cap = (unsigned)cap;
             }
             r = timed(HGS_K_ELEMENTWISE, [&]() -> int {
@@ -1916,15 +1756,15 @@ template <typename R> struct Engine : EngineBase {
                 if (was_not_fixed && st->iter >= st->fix_phase_iteration - 1 &&
                     st->false_run >= st->fix_phase_iteration)
                     st->fixed_phase = 1;
-                if ((st->fixed_phase && !have_pff) || was_not_fixed) p.store_phase = 1;
+                if ((st->fixed_phase && !state.have_pff()) || was_not_fixed) p.store_phase = 1;
             } else {
                 st->fixed_phase = 0;
             }
         }
         // :1601  "if not fixed or phase_ff is None: phase_ff = atan2(F)".  A phase stored in this very
         // iteration equals atan2(F), so "store + rebuild from F" is the same thing as using it.
-        if (st->fixed_phase && !have_pff) p.store_phase = 1;
-        p.use_fixed = (st->fixed_phase && have_pff && !p.store_phase) ? 1 : 0;
+        if (st->fixed_phase && !state.have_pff()) p.store_phase = 1;
+        p.use_fixed = (st->fixed_phase && state.have_pff() && !p.store_phase) ? 1 : 0;
         return p;
     }
 
@@ -1942,8 +1782,7 @@ template <typename R> struct Engine : EngineBase {
         double eff = 0;
         if (eff_host) eff = *eff_host;
         else {
-            HIPCHK(hipMemcpyAsync(&eff, dev, sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
+            if (int e = d2h(&eff, dev, sizeof(double))) return e;
         }
         if (eff > st->fix_phase_efficiency) st->fixed_phase = 1;
         return 0;
@@ -1967,6 +1806,18 @@ template <typename R> struct Engine : EngineBase {
         return c;
     }
 
+    // spot integration windows of `width` pixels around (x[k], y[k]), floored: each must stay on the grid.  ixy: the floored
+    // coordinates, x then y (may be null); msg: the caller's wording, with one %d for the spot
+    template <typename T> int check_windows(const T* x, const T* y, int n, int width, int32_t* ixy, const char* msg) {
+        const int flo = (int)std::floor(-(width - 1) / 2.0), fhi = flo + width - 1;
+        for (int k = 0; k < n; ++k) {
+            const int32_t xk = (int32_t)std::floor(x[k]), yk = (int32_t)std::floor(y[k]);
+            if (ixy) { ixy[k] = xk; ixy[n + k] = yk; }
+            if (xk + flo < 0 || yk + flo < 0 || xk + fhi >= g.Pw || yk + fhi >= g.Ph) return fail(HGS_ERR_ARG, msg, k);
+        }
+        return 0;
+    }
+
     int check_step(const hgs_step* st) {
         if (st->method < HGS_GS || st->method > HGS_WGS_TANH) return fail(HGS_ERR_ARG, "unknown method %d", st->method);
         if (st->feedback < HGS_FB_PIXEL || st->feedback > HGS_FB_EXTERNAL) return fail(HGS_ERR_ARG, "unknown feedback %d", st->feedback);
@@ -1975,13 +1826,8 @@ template <typename R> struct Engine : EngineBase {
             if (!has_spots) return fail(HGS_ERR_STATE, "spot feedback needs HGS_SPOT_INDEX / HGS_SPOT_AMP");
             if (st->feedback == HGS_FB_SPOT_WINDOW) {
                 if (st->spot_window < 1) return fail(HGS_ERR_ARG, "spot_window must be >= 1");
-                const int flo = (int)std::floor(-(st->spot_window - 1) / 2.0);
-                const int fhi = flo + st->spot_window - 1;
-                for (int n = 0; n < cfg.n_spots; ++n) {
-                    const int x = spot_xy_host[n], y = spot_xy_host[cfg.n_spots + n];
-                    if (x + flo < 0 || y + flo < 0 || x + fhi >= g.Pw || y + fhi >= g.Ph)
-                        return fail(HGS_ERR_ARG, "integration window of spot %d leaves the grid (IndexError in the reference)", n);
-                }
+                if (int e = check_windows(spot_xy_host.data(), spot_xy_host.data() + cfg.n_spots, cfg.n_spots, st->spot_window, nullptr,
+                                          "integration window of spot %d leaves the grid (IndexError in the reference)")) return e;
             }
         }
         return 0;
@@ -1989,12 +1835,12 @@ template <typename R> struct Engine : EngineBase {
 
     // general constraint on the materialised farfield
     int constraint_planned(hgs_step* st, const Plan& p) {
-        if (!ff || !farfield_valid) return fail(HGS_ERR_STATE, "farfield is not materialised");
+        if (!ff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "farfield is not materialised");
         if (int e = need_pff()) return e;
         if (int e = normalize_weights_now()) return e;
-        if (p.do_update) sparse_dirty = true;     // the general rules rewrite the weight array
+        if (p.do_update) state.general_rule_updated_weights();
         if (st->mraf_enabled && st->zero_mode) { if (int e = need_zw()) return e; }
-        if (st->mraf_enabled && st->fixed_phase && !have_pff && !p.store_phase)
+        if (st->mraf_enabled && st->fixed_phase && !state.have_pff() && !p.store_phase)
             return fail(HGS_ERR_STATE, "fixed_phase with MRAF needs a stored phase_ff (reference quirk A12)");
         CParams<R> cp = cparams(st, p);
         EwArgs<R> a{};
@@ -2044,7 +1890,7 @@ template <typename R> struct Engine : EngineBase {
             // the rebuild recomputes and stores phase_ff whenever it is not "use_fixed"
             hipLaunchKernelGGL(ew_rebuild<R>, eg, eb, 0, stream, a);
             HIPCHK(hipGetLastError());
-            have_pff = true;
+            state.phase_ff_stored();
             return 0;
         });
     }
@@ -2073,7 +1919,7 @@ template <typename R> struct Engine : EngineBase {
         if (cfg.kind != 0 || general || st->mraf_enabled || st->method == HGS_GS || st->feedback == HGS_FB_PIXEL) return false;
         if (!tun.sparse || opt_stepwise) return false;
         if (refresh_sparse()) return false;
-        return n_active_min > 0 && n_active_max * 4 <= g.Pw;
+        return active.n_min > 0 && active.n_max * 4 <= g.Pw;
     }
     // ---- executors of a ColumnPlan (column_plan.hpp: what is launched is decided there) ----
     PassFacts pass_facts(const hgs_step* st, const Plan& p, bool sparse_enabled) const {
@@ -2087,33 +1933,28 @@ template <typename R> struct Engine : EngineBase {
     int launch_dilated_forward() {
         return timed(HGS_K_COL_FWD, [&]() -> int {
             ColArgs<R> a = col_args();
-            a.col_list = col_list_d;
-            a.n_active = n_active_d_dev;
-            LCHK(launch_col<R>(g.Ph, C_FWD | C_STORE, dim3(list_blocks(base_facts(), n_active_d_max), B), stream, a));
+            a.col_list = dilated.list;
+            a.n_active = dilated.n_dev;
+            LCHK(launch_col<R>(g.Ph, C_FWD | C_STORE, dim3(list_blocks(base_facts(), dilated.n_max), B), stream, a));
             return 0;
         });
     }
     // the buffers a plan lists; f / cp: re-planned once where the device cannot give the farfield buffer of the float64 split form
     int acquire(ColumnPlan& cp, PassFacts& f) {
-        if (cp.need_ffb && !ffb_zeroed) {
-            if (!ffb) {
-                void* q = nullptr;
-                if (hipMalloc(&q, (size_t)B * g.Ph * g.Pw * sizeof(C)) == hipSuccess) ffb = static_cast<C*>(q);
-                else {
-                    (void)hipGetLastError();
-                    f.ffb_unavailable = true;
-                    cp = plan_column_pass(f);
-                }
+        if (cp.need_ffb && !state.ffb_zeroed()) {
+            if (ffb.ensure((size_t)B * g.Ph * g.Pw) != hipSuccess) {      // (tolerated: the two-pass form needs no such buffer)
+                f.ffb_unavailable = true;
+                cp = plan_column_pass(f);
             }
             if (cp.need_ffb) {
                 HIPCHK(hipMemsetAsync(ffb, 0, (size_t)B * g.Ph * g.Pw * sizeof(C), stream));
-                ffb_zeroed = true;
+                state.ffb_was_zeroed();
             }
         }
         // (dpartial: sized like wpartial)
-        if (cp.need_dpartial && !dpartial) { if (dalloc(&dpartial, (size_t)B * std::max(std::max(col_blocks, tile_blocks), n_cu * 3))) return HGS_ERR_DEVICE; }
-        if (cp.need_gh2 && !gh2) { if (dalloc(&gh2, (size_t)B * g.Sh * g.Pw)) return HGS_ERR_DEVICE; }
-        if (cp.need_nog_dev && !nog_dev) { if (dalloc(&nog_dev, (size_t)B)) return HGS_ERR_DEVICE; }
+        if (cp.need_dpartial) { if (int e = need_zeroed(dpartial, (size_t)B * std::max(std::max(col_blocks, tile_blocks), n_cu * 3))) return e; }
+        if (cp.need_gh2) { if (int e = need_zeroed(gh2, (size_t)B * g.Sh * g.Pw)) return e; }
+        if (cp.need_nog_dev) { if (int e = need_zeroed(nog_dev, (size_t)B)) return e; }
         return 0;
     }
     // the pre-pass of the single-inverse MRAF update (its own profile slot: a forward-only column launch)
@@ -2127,8 +1968,8 @@ template <typename R> struct Engine : EngineBase {
             if (cp.presum_col) {             // per-column, over the signal columns
                 pa.cp.weights_only = 1;
                 pa.cp.presum = 1;
-                pa.col_list = col_list_signal;
-                pa.n_active = n_signal_dev;
+                pa.col_list = signal.list;
+                pa.n_active = signal.n_dev;
                 pa.list_xmap = cp.prepass_list_xmap;
                 LCHK(launch_fused<R>(g.Ph, 0, grid, stream, pa));
             } else if constexpr (sizeof(R) == 4) {
@@ -2184,7 +2025,7 @@ template <typename R> struct Engine : EngineBase {
                 hipLaunchKernelGGL(stat_fill_neutral, dim3((unsigned)((stat_nslots + 255) / 256)), dim3(256), 0, stream,
                                    stat_partial, stat_nslots);
             }
-            if (l.listed) { a.col_list = col_list; a.n_active = n_active_dev; }
+            if (l.listed) { a.col_list = active.list; a.n_active = active.n_dev; }
             a.list_xmap = l.list_xmap ? 1 : 0;
             if (l.col_flags) a.col_flags = col_active;
             a.few_active = l.few_active ? 1 : 0;
@@ -2193,7 +2034,7 @@ template <typename R> struct Engine : EngineBase {
             if (l.nog_pass) {
                 if (int e = reduce(wpartial, l.grid, sums + 1 * B)) return e;
                 hipLaunchKernelGGL(nog_finalize<R>, dim3((B + 63) / 64), dim3(64), 0, stream, (const double*)(sums + 1 * B),
-                                   l.listed ? (const int*)n_active_dev : (const int*)nullptr, g.Ph, g.Pw, nog_dev, B);
+                                   l.listed ? (const int*)active.n_dev : (const int*)nullptr, g.Ph, g.Pw, nog_dev, B);
                 HIPCHK(hipGetLastError());
             }
             if (then_scale) {
@@ -2211,8 +2052,8 @@ template <typename R> struct Engine : EngineBase {
             ColArgs<R> nb = col_args();
             nb.ff = ffb;
             nb.gh = gh2;
-            nb.col_list = col_list_noise;
-            nb.n_active = n_noise_dev;
+            nb.col_list = noise.list;
+            nb.n_active = noise.n_dev;
             LCHK(launch_col<R>(g.Ph, C_LOAD | C_INV, dim3(cp.noise_inverse_grid, B), stream, nb));
             return 0;
         });
@@ -2232,14 +2073,12 @@ template <typename R> struct Engine : EngineBase {
         auto windows_needed = [&](const Plan& q) {
             return (st->feedback == HGS_FB_SPOT_WINDOW && q.do_update) || (groups & 2);
         };
-        farfield_valid = false;
-        w_unit = false;           // (spot_update writes the weights itself)
-        w_outside_scan = true;
+        state.spot_sparse_call_begins();
         Plan p = plan_iteration(st, hist ? hist : nullptr);
         if (int e = keep_prev_phase(p, n)) return e;
         if (!gh_holds(windows_needed(p) ? 2 : 1)) { if (int e = run_row(0, false, 0, windows_needed(p) ? 2 : 1)) return e; }
         for (int i = 0; i < n; ++i) {
-            gh_state = -1;
+            state.column_pass_begins();
             if (p.use_fixed || p.store_phase) { if (int e = need_pff()) return e; }
             const CParams<R> cprm = cparams(st, p);
             if (windows_needed(p)) { if (int e = launch_dilated_forward()) return e; }
@@ -2259,7 +2098,7 @@ template <typename R> struct Engine : EngineBase {
             const ColumnPlan cp = plan_spot_sparse_pass(pass_facts(st, p, true));      // (the weights were updated above)
             if (int e = launch_column(cp.main, cprm)) return e;
             if (stat_ctx) { if (int e = fused_stats_finish(i, cp)) return e; }
-            if (p.store_phase) have_pff = true;
+            if (p.store_phase) state.phase_ff_stored();
             if (stat_ctx) { if (int e = eff_gate_after(st, nullptr, stat_ctx->dev_out + ((size_t)i * 2 + st->efficiency_group) * B * 4)) return e; }
             st->iter++;
             Plan pn{0, 0, 0};
@@ -2286,7 +2125,7 @@ template <typename R> struct Engine : EngineBase {
         const bool fused = fused_ok(st) && !opt_stepwise;
         if (!fused && spot_sparse_ok(st)) return iterate_spot_sparse(st, n, hist);
         if (!fused) {
-            have_prev = false;           // the general operators keep HGS_PHASE_FF itself up to date
+            state.prev_phase_dropped();           // the general operators keep HGS_PHASE_FF itself up to date
             for (int i = 0; i < n; ++i) {
                 if (int e = n2f(0)) return e;
                 Plan p = plan_iteration(st, hist ? hist + i : nullptr);
@@ -2296,7 +2135,7 @@ template <typename R> struct Engine : EngineBase {
             }
             return 0;
         }
-        farfield_valid = false;
+        state.fused_call_begins();
         // Sparse targets: when few columns hold a non-zero weight/target, only those columns are
         // transformed (col_fused_kernel with a column list) and only they cross HBM between the two
         // kernels.  phase_ff (WGS-Kim) is then stored on the active columns only: nothing else can be
@@ -2304,7 +2143,7 @@ template <typename R> struct Engine : EngineBase {
         bool sp = false;
         if (tun.sparse) {
             if (int e = refresh_sparse()) return e;
-            sp = n_active_min > 0 && n_active_max * 2 <= g.Pw;
+            sp = active.n_min > 0 && active.n_max * 2 <= g.Pw;
         } else if (st->mraf_enabled && st->method != HGS_GS && tun.mraf_split && tun.gh2_mask && tile_geometry_ok() && g.Pw >= 4096) {
             // single-pass MRAF: which columns hold a NaN target (the noise part exists only there) -- a fact about the
             // target, scanned once per upload; the dense launches themselves still walk every column
@@ -2314,9 +2153,8 @@ template <typename R> struct Engine : EngineBase {
             // tile kernel (ColArgs::few_active) -- a fact about the target, scanned once per upload
             // (batches: the same scan says in which columns that kernel requests weights and targets at all; they now pay it
             //  too -- one scan launch and a device-to-host synchronisation per upload of weights or target, dense images included)
-            // (weights written behind the scan's back since -- spot feedback, a folded scale -- are scanned again here, once,
-            //  so that the flags are withheld for no longer than it takes to reach this line)
-            if (w_outside_scan && tun.empty_col_loads) sparse_dirty = true;
+            // (weights written behind the scan's back since are scanned again here, once: EngineState::w_outside_scan)
+            if (tun.empty_col_loads) state.rescan_if_written_outside();
             if (int e = refresh_sparse()) return e;
         }
         // "computational_spot" statistics on the sparse path: amp_ff is produced on the spot columns dilated
@@ -2335,7 +2173,7 @@ template <typename R> struct Engine : EngineBase {
         // (the previous call may have left G of these columns behind: gh_state, row_kernel MODE 3)
         if (!gh_holds(sp ? store_sparse : 0)) { if (int e = run_row(0, false, 0, sp ? store_sparse : 0)) return e; }
         for (int i = 0; i < n; ++i) {
-            gh_state = -1;          // the column pass turns G into H in place
+            state.column_pass_begins();
             if (p.use_fixed || p.store_phase) { if (int e = need_pff()) return e; }
             // facts -> plan: the column scans the form consults first (their counts feed the choice), then the plan itself
             PassFacts f = pass_facts(st, p, sp);
@@ -2355,8 +2193,8 @@ template <typename R> struct Engine : EngineBase {
             if (cp.second_pass) { if (int e = launch_column(cp.second, cprm)) return e; }
             if (int e = launch_noise_inverse(cp)) return e;
             if (stat_ctx) { if (int e = fused_stats_finish(i, cp)) return e; }
-            if (p.store_phase) have_pff = true;
-            if (p.do_update) { w_pending = true; w_unit = true; }       // (wscale: from this pass' partials, in the pass or in the row launch below)
+            if (p.store_phase) state.phase_ff_stored();
+            if (p.do_update) state.fused_update_done();
             if (stat_ctx) { if (int e = eff_gate_after(st, nullptr, stat_ctx->dev_out + ((size_t)i * 2 + st->efficiency_group) * B * 4)) return e; }
             st->iter++;
             Plan pn{0, 0, 0};
@@ -2411,18 +2249,12 @@ template <typename R> struct Engine : EngineBase {
             if (cfg.n_spots <= 0 || !xy || !has_spots) return fail(HGS_ERR_STATE, "spot statistics need spots");
             const int N = cfg.n_spots;
             ixy.resize(2 * N);
-            const int flo = (int)std::floor(-(width - 1) / 2.0), fhi = flo + width - 1;
-            for (int k = 0; k < N; ++k) {
-                ixy[k] = (int32_t)std::floor(xy[k]);
-                ixy[N + k] = (int32_t)std::floor(xy[N + k]);
-                if (ixy[k] + flo < 0 || ixy[N + k] + flo < 0 || ixy[k] + fhi >= g.Pw || ixy[N + k] + fhi >= g.Ph)
-                    return fail(HGS_ERR_ARG, "integration window of spot %d leaves the grid", k);
-            }
+            if (int e = check_windows(xy, xy + N, N, width, ixy.data(), "integration window of spot %d leaves the grid")) return e;
         }
         for (size_t k = 0; k < (size_t)n * 2 * B * 4; ++k) out[k] = NAN;
         const bool fused = (fused_ok(st) || spot_sparse_ok(st)) && !opt_stepwise;
         if (!fused) {
-            have_prev = false;
+            state.prev_phase_dropped();
             // general path: materialise, reduce, constrain -- one host read of a few doubles per iteration
             for (int i = 0; i < n; ++i) {
                 if (int e = n2f(0)) return e;
@@ -2442,38 +2274,32 @@ template <typename R> struct Engine : EngineBase {
         const int max_blocks = std::max(std::max(tile_blocks, col_blocks), n_cu * 3);
         const size_t nslots = (size_t)B * max_blocks * STAT_WAVES;
         stat_nslots = nslots;
-        if (!stat_partial) { if (dalloc(&stat_partial, nslots * STAT_N)) return HGS_ERR_DEVICE; }
-        if (!stat_tsum) { if (dalloc(&stat_tsum, (size_t)B)) return HGS_ERR_DEVICE; }
+        if (need_zeroed(stat_partial, nslots * STAT_N)) return HGS_ERR_DEVICE;
+        if (need_zeroed(stat_tsum, (size_t)B)) return HGS_ERR_DEVICE;
         if (groups & 2) { if (int e = need_aff()) return e; }
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&c.dev_out), (size_t)n * 2 * B * 4 * sizeof(double)));
-        int r = 0;
-        do {
-            if (groups & 2) {
-                if (hipMalloc(reinterpret_cast<void**>(&c.dxy), ixy.size() * sizeof(int)) != hipSuccess) { r = fail(HGS_ERR_DEVICE, "hipMalloc"); break; }
-                if (hipMemcpyAsync(c.dxy, ixy.data(), ixy.size() * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) { r = fail(HGS_ERR_DEVICE, "hipMemcpy"); break; }
-            }
-            hipLaunchKernelGGL(stat_fill_neutral, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, stream, stat_partial, nslots);
-            // sum T^2 (the fused path has no NaN targets)
-            hipLaunchKernelGGL(ew_sumsq<R>, dim3(ew_blocks, B), dim3(256), 0, stream, (const R*)t, P, epartial);
-            if (hipGetLastError() != hipSuccess) { r = fail(HGS_ERR_DEVICE, "statistics setup launch failed"); break; }
-            if ((r = reduce(epartial, ew_blocks, stat_tsum))) break;
-            stat_ctx = &c;
-            r = iterate(st, n, hist);
-            stat_ctx = nullptr;
-            if (r) break;
-            std::vector<double> h((size_t)n * 2 * B * 4);
-            if (hipMemcpyAsync(h.data(), c.dev_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess) { r = fail(HGS_ERR_DEVICE, "statistics read-back failed"); break; }
-            for (int i = 0; i < n; ++i)
-                for (int gidx = 0; gidx < 2; ++gidx)
-                    if (groups & (1 << gidx))
-                        std::memcpy(out + ((size_t)i * 2 + gidx) * B * 4, h.data() + ((size_t)i * 2 + gidx) * B * 4, (size_t)B * 4 * sizeof(double));
-        } while (0);
+        HIPCHK(c.dev_out.alloc((size_t)n * 2 * B * 4));
+        // (c's buffers are freed on every way out; launches that may still use them have drained by then)
+        struct Drain { hipStream_t s; ~Drain() { hipStreamSynchronize(s); } } drain{stream};
+        if (groups & 2) {
+            if (c.dxy.alloc(ixy.size()) != hipSuccess) return fail(HGS_ERR_DEVICE, "hipMalloc");
+            if (hipMemcpyAsync(c.dxy, ixy.data(), ixy.size() * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) return fail(HGS_ERR_DEVICE, "hipMemcpy");
+        }
+        hipLaunchKernelGGL(stat_fill_neutral, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, stream, stat_partial.get(), nslots);
+        // sum T^2 (the fused path has no NaN targets)
+        hipLaunchKernelGGL(ew_sumsq<R>, dim3(ew_blocks, B), dim3(256), 0, stream, (const R*)t, P, epartial.get());
+        if (hipGetLastError() != hipSuccess) return fail(HGS_ERR_DEVICE, "statistics setup launch failed");
+        if (int r = reduce(epartial, ew_blocks, stat_tsum)) return r;
+        stat_ctx = &c;
+        const int r = iterate(st, n, hist);
         stat_ctx = nullptr;
-        hipStreamSynchronize(stream);
-        if (c.dev_out) hipFree(c.dev_out);
-        if (c.dxy) hipFree(c.dxy);
-        return r;
+        if (r) return r;
+        std::vector<double> h((size_t)n * 2 * B * 4);
+        if (d2h(h.data(), c.dev_out, h.size() * sizeof(double))) return fail(HGS_ERR_DEVICE, "statistics read-back failed");
+        for (int i = 0; i < n; ++i)
+            for (int gidx = 0; gidx < 2; ++gidx)
+                if (groups & (1 << gidx))
+                    std::memcpy(out + ((size_t)i * 2 + gidx) * B * 4, h.data() + ((size_t)i * 2 + gidx) * B * 4, (size_t)B * 4 * sizeof(double));
+        return 0;
     }
 
     hipEvent_t timed_ev[2] = {nullptr, nullptr};      // hgs_iterate_timed: created once (a pair per call costs ~10 us)
@@ -2526,18 +2352,17 @@ template <typename R> struct Engine : EngineBase {
     }
 
     int stats(int group, int width, const double* xy, double* out) override {
-        if (!aff || !farfield_valid) return fail(HGS_ERR_STATE, "statistics need a materialised farfield");
+        if (!aff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "statistics need a materialised farfield");
         const int nb = std::min(ew_blocks, 1024);
         if (group == 0) {
             // persistent scratch: hipMalloc / hipFree per call would synchronise the device every iteration
-            if (!stats_scratch) { if (dalloc(&stats_scratch, (size_t)B * 1024 * 7 + (size_t)B * 2)) return HGS_ERR_DEVICE; }
+            if (need_zeroed(stats_scratch, (size_t)B * 1024 * 7 + (size_t)B * 2)) return HGS_ERR_DEVICE;
             double* d1 = stats_scratch;
             double* d_sfst = d1 + (size_t)B * nb * 7;
             hipLaunchKernelGGL(stats_pass1<R>, dim3(nb, B), dim3(256), 0, stream, (const R*)aff, (const R*)t, P, d1);
             HIPCHK(hipGetLastError());
             std::vector<double> h((size_t)B * nb * 7);
-            HIPCHK(hipMemcpyAsync(h.data(), d1, (size_t)B * nb * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
+            if (int e = d2h(h.data(), d1, (size_t)B * nb * 3 * sizeof(double))) return e;
             std::vector<double> sfst(2 * B), stf(B);
             for (int b = 0; b < B; ++b) {
                 double s0 = 0, s1 = 0, s2 = 0;
@@ -2551,8 +2376,7 @@ template <typename R> struct Engine : EngineBase {
             hipLaunchKernelGGL(stats_pass2<R>, dim3(nb, B), dim3(256), 0, stream, (const R*)aff, (const R*)t, P,
                                (const double*)d_sfst, d1);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(h.data(), d1, (size_t)B * nb * 7 * sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
+            if (int e = d2h(h.data(), d1, (size_t)B * nb * 7 * sizeof(double))) return e;
             for (int b = 0; b < B; ++b) {
                 double rmin = INFINITY, rmax = -INFINITY, emin = INFINITY, emax = -INFINITY, es = 0, es2 = 0, cnt = 0;
                 for (int i = 0; i < nb; ++i) {
@@ -2575,14 +2399,8 @@ template <typename R> struct Engine : EngineBase {
             const int N = cfg.n_spots;
             // window sums at floor(spot_knm) (take() floors, quirk A18); width 1 = the pixel itself
             std::vector<int32_t> ixy(2 * N);
-            const int flo = (int)std::floor(-(width - 1) / 2.0), fhi = flo + width - 1;
-            for (int n = 0; n < N; ++n) {
-                ixy[n] = (int32_t)std::floor(xy[n]);
-                ixy[N + n] = (int32_t)std::floor(xy[N + n]);
-                if (ixy[n] + flo < 0 || ixy[N + n] + flo < 0 || ixy[n] + fhi >= g.Pw || ixy[N + n] + fhi >= g.Ph)
-                    return fail(HGS_ERR_ARG, "integration window of spot %d leaves the grid", n);
-            }
-            if (!stats_dxy) { if (dalloc(&stats_dxy, (size_t)2 * N)) return HGS_ERR_DEVICE; }
+            if (int e = check_windows(xy, xy + N, N, width, ixy.data(), "integration window of spot %d leaves the grid")) return e;
+            if (need_zeroed(stats_dxy, (size_t)2 * N)) return HGS_ERR_DEVICE;
             int* dxy = stats_dxy;
             HIPCHK(hipMemcpyAsync(dxy, ixy.data(), 2 * N * sizeof(int), hipMemcpyHostToDevice, stream));
             SpotArgs<R> s{};
@@ -2607,16 +2425,16 @@ template <typename R> struct Engine : EngineBase {
 
     int set_option(int option, int value) override {
         // (a change of the column policy may change which columns the next launch expects in gh)
-        if (option == HGS_OPT_SPARSE_COLUMNS || option == HGS_OPT_FORCE_STEPWISE || option == HGS_OPT_TILE_KERNEL) gh_state = -1;
+        if (option == HGS_OPT_SPARSE_COLUMNS || option == HGS_OPT_FORCE_STEPWISE || option == HGS_OPT_TILE_KERNEL) state.column_policy_changed();
         switch (option) {
             case HGS_OPT_SPARSE_COLUMNS: tun.sparse = value ? 1 : 0; return 0;
             case HGS_OPT_FORCE_STEPWISE: opt_stepwise = value ? 1 : 0; return 0;
-            case HGS_OPT_TILE_KERNEL: tun.tile = value ? 1 : 0; sparse_dirty = true; return 0;
+            case HGS_OPT_TILE_KERNEL: tun.tile = value ? 1 : 0; state.scan_policy_changed(); return 0;
             case HGS_OPT_SEPARABLE: opt_separable = value ? 1 : 0; return 0;
             case HGS_OPT_SEPARABLE_MIN_SPOTS: opt_sep_min = value > 0 ? value : 1; return 0;
             case HGS_OPT_RUN_KERNELS: opt_run = value ? 1 : 0; return 0;
             case HGS_OPT_EMPTY_COL_LOADS: tun.empty_col_loads = value ? 1 : 0; return 0;
-            case HGS_OPT_KEEP_PREV_PHASE: opt_prev_phase = value ? 1 : 0; if (!value) have_prev = false; return 0;
+            case HGS_OPT_KEEP_PREV_PHASE: opt_prev_phase = value ? 1 : 0; if (!value) state.prev_phase_dropped(); return 0;
             case HGS_OPT_ROCTX:
                 if (value && !g_roctx.load()) return fail(HGS_ERR_UNSUPPORTED, "no roctx library (librocprofiler-sdk-roctx / libroctx64) found");
                 opt_roctx = value ? 1 : 0;

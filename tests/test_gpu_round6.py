@@ -295,6 +295,48 @@ def test_mraf_single_inverse_on_the_per_column_kernel(dt, shape, slm, method, ex
         assert ep < 5e-3 and ew < 5e-3, errs
 
 
+def test_weight_writers_send_one_mraf_update_through_the_old_form_a_target_none():
+    """
+    Who clears "the stored weights are normalised" (what the single-inverse MRAF update builds on), end to end, at the
+    smallest geometry where that form runs: float32, pad (1024, 1024), SLM (300, 400) -- the per-column kernel, pre-pass
+    ``col_fused_kernel ... list`` over the signal columns.  Three bodies, then in turn a weight reset, a host upload of
+    weights and a new target of the same NaN layout, each followed by two more bodies.
+
+    Launches per two-body call, as the code has it and as measured before the engine's host state was gathered into
+    EngineState (the same engine, one commit earlier):
+      after reset_weights:  1 pre-pass, 3 unlisted col_fused_kernel launches (body 1 in two passes, body 2 in one), 0 joins
+      after h.weights = :   1 pre-pass, 3 unlisted launches, 0 joins
+      after a new target:   2 pre-passes, 2 unlisted launches, 0 joins
+    (1024 columns are fewer than the split forms take, so the old form here is the two-pass one: ``row_kernel SPLIT`` and
+    ``col_kernel MODE=24`` -- how the old form shows at 4096 columns and more -- stay at zero throughout.)
+    """
+    shape, slm, n = (1024, 1024), (300, 400), 1024
+    target = _mraf_frame(shape, np.float32, box=False)
+    h = Hologram(target.copy(), phase=synth.seed_phase(17, slm), slm_shape=slm, dtype=np.float32, engine_options={L.OPT_SPARSE_COLUMNS: 0})
+    h.optimize("WGS-Leonardo", maxiter=3, verbose=False, mraf_factor=0.5)
+    d = dispatch_of(h)
+    assert d.count("col_fused_kernel", N=n, RULE=0, flags=["list"]) == 1, d          # body 3: the single-inverse form is running
+
+    def two_bodies():
+        h.optimize("WGS-Leonardo", maxiter=2, verbose=False, mraf_factor=0.5)
+        d = dispatch_of(h)
+        assert np.all(np.isfinite(h.phase))
+        got = (d.count("col_fused_kernel", N=n, flags=["list"]), d.count("col_fused_kernel", N=n, without=["list"]),
+               d.count("row_kernel", SPLIT=True) + d.count("col_kernel", MODE=24))
+        print("dispatch after", got, "\n", d)
+        return got
+
+    h.reset_weights()
+    assert two_bodies() == (1, 3, 0)
+    h.weights = np.array(h.weights, copy=True) * 3.0
+    assert two_bodies() == (1, 3, 0)
+    other = target.copy()
+    other[np.isfinite(target) & (target > 0)] = synth.random_target(22, shape, 0.2, 1.0)[np.isfinite(target) & (target > 0)]
+    h.set_target(other)
+    assert two_bodies() == (2, 2, 0)
+    h._release_engine()
+
+
 def test_fixed_phase_without_a_stored_phase_on_an_mraf_target_raises_like_the_reference():
     """
     Reference quirk A12 (SURVEY appendix): a WGS-Kim run fixes the phase, ``reset()`` keeps the flags and forgets ``phase_ff``;
