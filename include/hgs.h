@@ -254,6 +254,17 @@ int hgs_sync(hgs_engine* e);
  *   pad_h >= 4096, the half-width col_tile2_kernel at pad_h = 4096 and 2048); 0 forces the per-column kernel at every size.
  * HGS_OPT_SEPARABLE (default 1), HGS_OPT_SEPARABLE_MIN_SPOTS (default 96): kind 1, run the two transforms as
  *   complex GEMMs on the matrix cores when the basis and the grid factorise; 0 forces the direct kernels.
+ * HGS_OPT_SEP_WORKGROUPS (default 0): kind 1, the workgroups of each of the two stream-K GEMMs (cgemm_streamk).  The line of
+ *   tiles * KT k-steps of a GEMM is cut into G equal shares; 0 means G = min(2 * #CU, tiles * KT), a value v > 0 means
+ *   G = min(v, 2 * #CU, tiles * KT) -- the schedule a device with fewer compute units (a partition) would run, which the
+ *   tests use to reach every regime of the schedule at small shapes (a workgroup that walks whole tiles, ranges that cross
+ *   or end on a tile boundary, several workgroups per tile).  Results under any two values differ only in how fp32 partial
+ *   sums are grouped.  Negative values return HGS_ERR_ARG.  Set after the kernels were uploaded, the tables of the
+ *   schedule and the two buffers of partial planes whose size follows it are rebuilt at once (the stream drains first).
+ *   hgs_dispatch_read marks cgemm_streamk launches whose G the option holds below min(2 * #CU, tiles * KT) with `sk_cap`.
+ *   Pinned by tests/test_streamk_gemm.py: under every value both transforms stay within 2e-5 (farfield) / 1e-4 (phase
+ *   phasor) of float64 direct summation in every 128-wide output tile, a batch equals its single runs bit for bit, and
+ *   0 after a cap gives the uncapped results back bit for bit; the schedule itself by tests/test_streamk_schedule.py.
  * HGS_OPT_RUN_KERNELS (default 1): kind 1, fp32, regular pixel grid and a phase polynomial of degree <= 2 (any basis of
  *   tilts, focus and astigmatisms, separable or not): the direct transforms advance exp(i phi) along runs of 16 pixels by
  *   a two-term recurrence instead of evaluating the polynomial, sin and cos per pixel; 0 forces the per-pixel kernels.
@@ -284,7 +295,7 @@ int hgs_sync(hgs_engine* e);
  *   general operators keep HGS_PHASE_FF itself up to date and hold no previous phase. */
 enum { HGS_OPT_SPARSE_COLUMNS = 1, HGS_OPT_FORCE_STEPWISE = 2, HGS_OPT_TILE_KERNEL = 3, HGS_OPT_SEPARABLE = 4,
        HGS_OPT_SEPARABLE_MIN_SPOTS = 5, HGS_OPT_ROCTX = 6, HGS_OPT_RUN_KERNELS = 7, HGS_OPT_KEEP_PREV_PHASE = 8,
-       HGS_OPT_EMPTY_COL_LOADS = 9 };
+       HGS_OPT_EMPTY_COL_LOADS = 9, HGS_OPT_SEP_WORKGROUPS = 10 };
 int hgs_set_option(hgs_engine* e, int option, int value);
 
 /* Timing support for bench.py: per-kernel HIP-event timing on the engine stream. */

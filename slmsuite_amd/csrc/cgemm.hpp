@@ -14,6 +14,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "streamk_schedule.hpp"
+
 namespace hgs {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -258,14 +260,7 @@ struct CgemmSkArgs {
     float2* part;          // [batch][tiles_n * 2 * planes][ldP]
     int ldP;
 };
-__host__ __device__ inline long long sk_begin(long long total, int G, int w) { return total * w / G; }
-// workgroup whose range [sk_begin(w), sk_begin(w + 1)) holds step idx
-__host__ __device__ inline int sk_owner(long long idx, long long total, int G) {
-    long long w = idx * G / total;
-    while (sk_begin(total, G, (int)w + 1) <= idx) ++w;
-    while (sk_begin(total, G, (int)w) > idx) --w;
-    return (int)w;
-}
+// sk_begin / sk_owner / sk_fill: streamk_schedule.hpp (plain C++, swept on the host by tests/test_streamk_schedule.py)
 
 // sum over the 32 lanes of each half of the wave (row_shr 1, 2, 4, 8 inside the rows of 16, row_bcast:15 from row 0 to 1
 // and from row 2 to 3): lanes 31 and 63 end up with the totals of their halves

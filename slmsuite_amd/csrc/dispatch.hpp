@@ -21,6 +21,7 @@ enum : unsigned {
     DF_STATS = 32u,      // in-pass statistics requested (ColArgs::do_stats)
     DF_NF_OUT = 64u,     // complex nearfield kept (MultiplaneHologram)
     DF_COL_FLAGS = 128u, // the column scan's flags go with the launch (ColArgs::col_flags)
+    DF_SK_CAP = 256u,    // cgemm_streamk: HGS_OPT_SEP_WORKGROUPS holds the grid below min(2 * #CU, tiles * KT)
 };
 
 struct DispatchSite {

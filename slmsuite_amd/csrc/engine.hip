@@ -85,7 +85,7 @@ thread_local DispatchLog* g_dispatch = nullptr;
 // one line per (kernel instance, run-time flags): "family<P0=v0,...> flag ...\tcount\n".  The argument values come from
 // __PRETTY_FUNCTION__ of dispatch_site<Fam, R, V...>: "... [Fam = hgs::KTile, R = float, V = <4096, 1, 6, false, false, 1, 0>]"
 std::string DispatchLog::text() const {
-    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags"};
+    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags", "sk_cap"};
     std::string out;
     for (const Ent& e : v) {
         std::vector<std::string> vals;
@@ -226,6 +226,7 @@ template <typename R> struct Engine : EngineBase {
     int opt_stepwise = 0;                  // HGS_OPT_FORCE_STEPWISE
     int opt_separable = 1;                 // HGS_OPT_SEPARABLE
     int opt_sep_min = 96;                  // smallest spot count the matrix-core form is used for (tools/sep_crossover.py)
+    int opt_sep_wg = 0;                    // HGS_OPT_SEP_WORKGROUPS: cap on the workgroups of each stream-K GEMM (0 = 2 * #CU)
     int opt_roctx = 0;                     // HGS_OPT_ROCTX: roctx ranges around the operators
     // what the buffers currently hold (G left behind, farfield, phase_ff, the weights' norm, the column lists): engine_state.hpp
     EngineState state;
@@ -287,6 +288,7 @@ template <typename R> struct Engine : EngineBase {
     DevBuf<double> sep_norm;     // [B][ceil(N/4)]
     int sep_split1 = 1, sep_kper1 = 0, sep_split2 = 1, sep_kper2 = 0, sep_degx = 0, sep_degy = 0;
     // stream-K schedule of the two GEMMs (cgemm_streamk): sep_split1 / sep_split2 are then the partial planes of C
+    unsigned sk_flag1 = 0, sk_flag2 = 0;   // DF_SK_CAP where the option holds G below min(2 * #CU, steps)
     int sk_G1 = 0, sk_G2 = 0, sk_kt1 = 0, sk_kt2 = 0, sk_tm1 = 0, sk_tn1 = 0, sk_tm2 = 0, sk_tn2 = 0;
     DevBuf<int> sk_tab;          // [first_wg 1][nseg 1][first_wg 2][nseg 2]
     int sep_Np = 0, sep_Hp = 0, sep_Wp = 0, sep_Wk = 0, sep_Nk = 0;   // padded leading dimensions / row counts
@@ -821,6 +823,32 @@ template <typename R> struct Engine : EngineBase {
         HIPCHK(hipGetLastError());
         return 0;
     }
+    // stream-K: the (tile, k tile) steps of each GEMM in G = min(HGS_OPT_SEP_WORKGROUPS or 2 * #CU, 2 * #CU, steps) equal shares
+    // (at most one workgroup per step: every workgroup owns work, the owners of a tile are consecutive); per tile the first
+    // workgroup and the number of partial planes it is spread over (consumers add exactly those), and the two buffers of
+    // partial results, whose size follows the planes.  Called when the tables are first made and when the option changes.
+    int sk_retable() {
+        const int H = g.Sh, W = g.Sw;
+        const int t1 = sk_tm1 * sk_tn1, t2 = sk_tm2 * sk_tn2;
+        const long long full = 2 * n_cu, want = opt_sep_wg > 0 ? std::min<long long>(opt_sep_wg, full) : full;
+        const long long steps1 = (long long)t1 * sk_kt1, steps2 = (long long)t2 * sk_kt2;
+        sk_G1 = (int)std::min(want, steps1);
+        sk_G2 = (int)std::min(want, steps2);
+        sk_flag1 = sk_G1 < std::min(full, steps1) ? DF_SK_CAP : 0u;
+        sk_flag2 = sk_G2 < std::min(full, steps2) ? DF_SK_CAP : 0u;
+        std::vector<int> tab((size_t)2 * (t1 + t2));
+        sep_split1 = sk_fill(t1, sk_kt1, sk_G1, tab.data(), tab.data() + t1);
+        sep_split2 = sk_fill(t2, sk_kt2, sk_G2, tab.data() + 2 * t1, tab.data() + 2 * t1 + t2);
+        // (launches on the stream may still read what a change of the option replaces)
+        HIPCHK(sk_tab.release(stream));
+        HIPCHK(sep_c1.release(stream));
+        HIPCHK(sep_c2.release(stream));
+        HIPCHK(sk_tab.alloc(tab.size()));
+        if (int e_ = h2d(sk_tab, tab.data(), tab.size() * sizeof(int))) return e_;
+        HIPCHK(sep_c1.alloc(sk_part_elems(B, sk_tn1, sep_split1, (size_t)sep_Np)));
+        HIPCHK(sep_c2.alloc(sk_c_elems(B, sep_split2, (size_t)H, (size_t)W)));
+        return 0;
+    }
     int sep_refresh_impl() {
         c_sep = false;
         if (sizeof(R) != 4 || cfg.kind != 1) return 0;
@@ -842,32 +870,10 @@ template <typename R> struct Engine : EngineBase {
         if (!sep_c) {
             // operands of the matrix-core GEMM are padded to whole tiles (zero filled once, never rewritten)
             auto up = [](int v, int q) { return (v + q - 1) / q * q; };
-            // stream-K: the (tile, k tile) steps of each GEMM in 2 * #CU equal shares; per tile the first workgroup and the
-            // number of partial planes it is spread over (consumers add exactly those)
             sk_tm1 = (N + CG_BM - 1) / CG_BM; sk_tn1 = (H + CG_BN - 1) / CG_BN; sk_kt1 = (W + CG_BK - 1) / CG_BK;
             sk_tm2 = (H + CG_BM - 1) / CG_BM; sk_tn2 = (W + CG_BN - 1) / CG_BN; sk_kt2 = (N + CG_BK - 1) / CG_BK;
-            {
-                const int t1 = sk_tm1 * sk_tn1, t2 = sk_tm2 * sk_tn2;
-                std::vector<int> tab((size_t)2 * (t1 + t2));
-                // (at most one workgroup per step: every workgroup owns work, the owners of a tile are consecutive)
-                sk_G1 = (int)std::min<long long>(2 * n_cu, (long long)t1 * sk_kt1);
-                sk_G2 = (int)std::min<long long>(2 * n_cu, (long long)t2 * sk_kt2);
-                auto fill = [&](int tiles, int KT, int G, int* first, int* nseg) {
-                    const long long total = (long long)tiles * KT;
-                    int planes = 1;
-                    for (int t = 0; t < tiles; ++t) {
-                        first[t] = sk_owner((long long)t * KT, total, G);
-                        nseg[t] = sk_owner((long long)(t + 1) * KT - 1, total, G) - first[t] + 1;
-                        planes = std::max(planes, nseg[t]);
-                    }
-                    return planes;
-                };
-                sep_split1 = fill(t1, sk_kt1, sk_G1, tab.data(), tab.data() + t1);
-                sep_split2 = fill(t2, sk_kt2, sk_G2, tab.data() + 2 * t1, tab.data() + 2 * t1 + t2);
-                HIPCHK(sk_tab.alloc(tab.size()));
-                if (int e_ = h2d(sk_tab, tab.data(), tab.size() * sizeof(int))) return e_;
-            }
             sep_Np = up(N, CG_BM); sep_Hp = up(H, CG_BN); sep_Wp = up(W, CG_BN);
+            if (int e_ = sk_retable()) return e_;
             sep_Wk = sk_kt1 * CG_BK;
             sep_Nk = sk_kt2 * CG_BK;
             HIPCHK(sep_c.alloc(c.size()));
@@ -877,13 +883,13 @@ template <typename R> struct Engine : EngineBase {
             if (dalloc(sep_ey, (size_t)N * H)) return HGS_ERR_DEVICE;
             if (dalloc(sep_nfT, (size_t)B * sep_Wk * sep_Hp)) return HGS_ERR_DEVICE;  // [B][Wk][Hp]
             if (dalloc(sep_b2, (size_t)B * sep_Nk * sep_Hp)) return HGS_ERR_DEVICE;   // [B][Nk][Hp]
-            HIPCHK(sep_c1.alloc((size_t)B * sk_tn1 * 2 * sep_split1 * sep_Np));
-            HIPCHK(sep_c2.alloc((size_t)B * sep_split2 * H * W));
             HIPCHK(sep_norm.alloc((size_t)B * ((N + 255) / 256)));
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cgemm_streamk<0>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)CG_LDS_BYTES));
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cgemm_streamk<1>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)CG_LDS_BYTES));
+        } else if (!sk_tab || !sep_c1 || !sep_c2) {      // (a change of HGS_OPT_SEP_WORKGROUPS that the device could not follow)
+            if (int e_ = sk_retable()) return e_;
         }
         HIPCHK(hipMemcpyAsync(sep_c, c.data(), c.size() * sizeof(double), hipMemcpyHostToDevice, stream));
         HIPCHK(hipMemcpyAsync(sep_g, xs_host.data(), (size_t)W * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -908,11 +914,11 @@ template <typename R> struct Engine : EngineBase {
     // the result with E over its columns into `part` instead of storing it (n2f)
     int launch_cgemm(const float* A, size_t planeA, const float* Bm, size_t planeB, float2* C, int M, int N, int KT, int lda, int ldb,
                      int tiles_m, int tiles_n, int planes, const int* first_wg, int G, size_t strideA, size_t strideB,
-                     const float2* E = nullptr, int ldE = 0, float2* part = nullptr, int ldP = 0) {
+                     unsigned cap_flag, const float2* E = nullptr, int ldE = 0, float2* part = nullptr, int ldP = 0) {
         CgemmSkArgs a{A, A + planeA, Bm, Bm + planeB, C, M, N, KT, lda, ldb, tiles_m, tiles_n, planes, first_wg, strideA, strideB,
                       E, ldE, part, ldP};
-        if (E) { dispatch_note(dispatch_site<KCgemm, float, 1>(), bflag()); hipLaunchKernelGGL(cgemm_streamk<1>, dim3(G, B), dim3(256), CG_LDS_BYTES, stream, a); }
-        else { dispatch_note(dispatch_site<KCgemm, float, 0>(), bflag()); hipLaunchKernelGGL(cgemm_streamk<0>, dim3(G, B), dim3(256), CG_LDS_BYTES, stream, a); }
+        if (E) { dispatch_note(dispatch_site<KCgemm, float, 1>(), bflag() | cap_flag); hipLaunchKernelGGL(cgemm_streamk<1>, dim3(G, B), dim3(256), CG_LDS_BYTES, stream, a); }
+        else { dispatch_note(dispatch_site<KCgemm, float, 0>(), bflag() | cap_flag); hipLaunchKernelGGL(cgemm_streamk<0>, dim3(G, B), dim3(256), CG_LDS_BYTES, stream, a); }
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -926,7 +932,7 @@ template <typename R> struct Engine : EngineBase {
         const int t1 = sk_tm1 * sk_tn1;
         if (int e = launch_cgemm(reinterpret_cast<const float*>(sep_exT.get()), (size_t)sep_Wk * sep_Np,
                                  reinterpret_cast<const float*>(sep_nfT.get()), (size_t)sep_Wk * sep_Hp, nullptr, N, H, sk_kt1, sep_Np, sep_Hp,
-                                 sk_tm1, sk_tn1, sep_split1, sk_tab, sk_G1, 0, (size_t)2 * sep_Wk * sep_Hp,
+                                 sk_tm1, sk_tn1, sep_split1, sk_tab, sk_G1, 0, (size_t)2 * sep_Wk * sep_Hp, sk_flag1,
                                  (const float2*)sep_ey, H, sep_c1, sep_Np)) return e;
         const int nred = (N + 255) / 256;
         hipLaunchKernelGGL(sep_n2f_sum<R>, dim3(nred, B), dim3(256), 0, stream, (const float2*)sep_c1, sep_Np, sep_split1,
@@ -945,7 +951,7 @@ template <typename R> struct Engine : EngineBase {
         const int t1 = sk_tm1 * sk_tn1, t2 = sk_tm2 * sk_tn2;
         if (int e = launch_cgemm(reinterpret_cast<const float*>(sep_b2.get()), (size_t)sep_Nk * sep_Hp,
                                  reinterpret_cast<const float*>(sep_ex.get()), (size_t)sep_Nk * sep_Wp, sep_c2, H, W, sk_kt2, sep_Hp, sep_Wp,
-                                 sk_tm2, sk_tn2, sep_split2, sk_tab + 2 * t1, sk_G2, (size_t)2 * sep_Nk * sep_Hp, 0)) return e;
+                                 sk_tm2, sk_tn2, sep_split2, sk_tab + 2 * t1, sk_G2, (size_t)2 * sep_Nk * sep_Hp, 0, sk_flag2)) return e;
         hipLaunchKernelGGL(sep_f2n_finish<R>, dim3((unsigned)((S + 255) / 256), B), dim3(256), 0, stream, (const float2*)sep_c2,
                            sep_split2, (const int*)(sk_tab + 2 * t1 + t2), sk_tm2, W, S,
                            has_kern ? (const R*)kern : (const R*)nullptr, phase, nf_out);
@@ -2432,6 +2438,14 @@ template <typename R> struct Engine : EngineBase {
             case HGS_OPT_TILE_KERNEL: tun.tile = value ? 1 : 0; state.scan_policy_changed(); return 0;
             case HGS_OPT_SEPARABLE: opt_separable = value ? 1 : 0; return 0;
             case HGS_OPT_SEPARABLE_MIN_SPOTS: opt_sep_min = value > 0 ? value : 1; return 0;
+            case HGS_OPT_SEP_WORKGROUPS:
+                if (value < 0) return fail(HGS_ERR_ARG, "HGS_OPT_SEP_WORKGROUPS must be 0 (2 x #CU) or a positive workgroup count, got %d", value);
+                if (value == opt_sep_wg) return 0;
+                opt_sep_wg = value;
+                // the tables exist already: rebuild them and the plane buffers they size
+                if (sep_c)
+                    if (int e_ = sk_retable()) { c_sep = false; return e_; }
+                return 0;
             case HGS_OPT_RUN_KERNELS: opt_run = value ? 1 : 0; return 0;
             case HGS_OPT_EMPTY_COL_LOADS: tun.empty_col_loads = value ? 1 : 0; return 0;
             case HGS_OPT_KEEP_PREV_PHASE: opt_prev_phase = value ? 1 : 0; if (!value) state.prev_phase_dropped(); return 0;

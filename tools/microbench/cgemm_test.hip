@@ -14,12 +14,7 @@ static int run_sk(const float* dA, size_t planeA, const float* dB, size_t planeB
     const long long total = (long long)tiles * KT;
     if (G > total) G = (int)total;            // every workgroup owns at least one step: the owners of a tile are consecutive
     std::vector<int> first(tiles), nseg(tiles);
-    int planes = 1;
-    for (int t = 0; t < tiles; ++t) {
-        first[t] = sk_owner((long long)t * KT, total, G);
-        nseg[t] = sk_owner((long long)(t + 1) * KT - 1, total, G) - first[t] + 1;
-        planes = std::max(planes, nseg[t]);
-    }
+    const int planes = sk_fill(tiles, KT, G, first.data(), nseg.data());
     int* dF;
     hipMalloc(&dF, tiles * 4);
     hipMemcpy(dF, first.data(), tiles * 4, hipMemcpyHostToDevice);
