@@ -55,6 +55,14 @@ __device__ __forceinline__ void trace_event(int& n, int ev) {
             (t & 0x00ffffffffffffffull) | ((unsigned long long)ev << 56);
     ++n;
 }
+// at the end of a kernel: the workgroup's nev events (128 per wave) from LDS into its slice of a buffer of the caller's
+__device__ __forceinline__ void trace_dump(void* out, int nev) {
+    extern __shared__ __attribute__((aligned(16))) char trace_smem[];
+    __syncthreads();
+    unsigned long long* dst = reinterpret_cast<unsigned long long*>(out) + (size_t)blockIdx.x * nev;
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(trace_smem + HGS_TRACE_OFF);
+    for (int i = threadIdx.x; i < nev; i += blockDim.x) dst[i] = src[i];
+}
 #define HGS_T(n, ev) trace_event(n, ev)
 #else
 #define HGS_T(n, ev) ((void)0)

@@ -363,6 +363,24 @@ __device__ __forceinline__ double pow_lean(double x, double c) {
     return x == 0.0 ? (c < 0 ? (double)INFINITY : 0.0) : r;
 }
 
+// 1 / sqrt(x) from the hardware instruction (1 ulp), pre-scaled where x is too small for it (v_rsq_f32 takes
+// denormal inputs as zero): the values of rsqrtf() without its inlined control flow
+__device__ __forceinline__ float rsqrt_full(float x) {
+    const bool tiny = x < 0x1p-100f;
+    const float r = __builtin_amdgcn_rsqf(tiny ? x * 0x1p+100f : x);
+    return tiny ? r * 0x1p+50f : r;
+}
+// float64: the hardware estimate and two Newton steps (x > 0; a sqrt and a division in double are some fifty instructions)
+__device__ __forceinline__ double rsqrt_full(double x) {
+    const bool tiny = x < 0x1p-900;
+    const double xs = tiny ? x * 0x1p+200 : x;
+    double y = __builtin_amdgcn_rsq(xs);
+    const double h = 0.5 * xs;
+    y = __builtin_fma(y, __builtin_fma(-h * y, y, 0.5), y);
+    y = __builtin_fma(y, __builtin_fma(-h * y, y, 0.5), y);
+    return tiny ? y * 0x1p+100 : y;
+}
+
 // (|F| c / T)^-p for the Leonardo / Kim rule of the fused kernels, from |F|^2: the ratio is formed FIRST (log2 of the
 // three factors separately cancels ~20 against ~20 and leaves 1e-6 relative noise per update).
 template <typename R> __device__ __forceinline__ R leonardo_factor(R p2, R t, R inv_fnorm, R p_exp) {
@@ -410,6 +428,50 @@ __device__ __forceinline__ R weight_factor(int method, R fb, R t, R p_exp, R p_f
     return fc;
 }
 
+// ---- the per-pixel step of the fused column kernels, piece by piece ------------------------------------
+// col_fused_kernel, col_tile_kernel, col_presum_kernel and col_tile2_kernel apply the same step to a transformed value
+// F; their loop bodies differ in control flow only.  Each rule here is spelled here and nowhere else.
+// tools/isa_diff.sh is the check that a change to the SHAPE of these helpers leaves the kernels' code as it was:
+// operands passed by reference below are so because by value it did not.
+//
+// Sparse targets (spot arrays): where weight and target are both zero the rule leaves the weight at zero (T == 0 ->
+// factor 1, :1841) and the constrained field is w * e^{i phi} = 0.  True when that holds for the whole wave, so that
+// the skip is a scalar branch.  (Callers do not skip when phase_ff or amp_ff of every pixel must be produced.)
+template <typename R> __device__ __forceinline__ bool wave_all_zero(const R& w, const R& t) {
+    return __builtin_amdgcn_ballot_w64(w != (R)0 || t != (R)0) == 0;
+}
+// The Leonardo / Kim factor with its guards: T == 0 -> 1 (:1841); inf (:1840, :1867) and nan (:1843) -> 1.  Evaluated
+// for every lane and selected: a branch per pixel splits the pass over a lane's 16 pixels into 16 blocks.
+template <typename R> __device__ __forceinline__ R leonardo_guarded(R p2, R t, R inv_fnorm, R p_exp) {
+    const R fc = leonardo_factor<R>(p2, t, inv_fnorm, p_exp);
+    return (t != (R)0 && fc < (R)INFINITY) ? fc : (R)1;
+}
+// a weight that came out NaN restarts from a small positive value (:1873)
+template <typename R> __device__ __forceinline__ R nan_floor(R w) { return is_nan(w) ? (R)0.0001 : w; }
+// exp(i * atan2(F)) == F / |F| from p2 = |F|^2, without the atan2 / sincos pair; atan2(0, 0) = 0 (quirk A6)
+template <typename R> __device__ __forceinline__ Cx<R> unit_phasor(Cx<R> F, R p2) {
+    const R inv = rsqrt_full(p2);
+    return mk<R>((p2 > (R)0) ? F.x * inv : (R)1, (p2 > (R)0) ? F.y * inv : (R)0);
+}
+// pixel m of a lane among the stored phases it fetched four at a time (q holds pixels 4 * (m / 4) .. + 3)
+template <int M> __device__ __forceinline__ float quad_at(float4 q) {
+    return (M % 4 == 0) ? q.x : (M % 4 == 1) ? q.y : (M % 4 == 2) ? q.z : q.w;
+}
+// the scheduler may interleave the rule evaluation of G consecutive pixels of a lane, no more (HGS_*CONS_GROUP*)
+template <int M, int G> __device__ __forceinline__ void sched_fence_every() {
+    if constexpr (M % G == G - 1) __builtin_amdgcn_sched_barrier(0);
+}
+// PHASE 1: the stored phase leaves four pixels (16 contiguous bytes) at a time, behind pixel M = 3, 7, 11, 15 --
+// sixteen of them kept until after the loop put the 4096 / 8192-point RULE 1 instances 12 / 8 registers over their 256
+template <int T, int M, typename R>
+__device__ __forceinline__ void store_phase_quad(R* pfc, int j, const R& p0, const R& p1, const R& p2, const R& p3) {
+    pfc[lane_pos<T>(j, M - 3)] = p0;
+    pfc[lane_pos<T>(j, M - 2)] = p1;
+    pfc[lane_pos<T>(j, M - 1)] = p2;
+    pfc[lane_pos<T>(j, M)] = p3;
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // ---- raw buffer accesses ------------------------------------------------------------------------------
 // One resource per array (row): the lane part of an address is ONE VGPR offset for all the registers of a lane,
 // the register part an SGPR offset, and the range check of the resource does the predication -- an element
@@ -440,24 +502,6 @@ __device__ __forceinline__ int uniform_load_i32(const int* p) {
     asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
     return v;
 }
-// 1 / sqrt(x) from the hardware instruction (1 ulp), pre-scaled where x is too small for it (v_rsq_f32 takes
-// denormal inputs as zero): the values of rsqrtf() without its inlined control flow
-__device__ __forceinline__ float rsqrt_full(float x) {
-    const bool tiny = x < 0x1p-100f;
-    const float r = __builtin_amdgcn_rsqf(tiny ? x * 0x1p+100f : x);
-    return tiny ? r * 0x1p+50f : r;
-}
-// float64: the hardware estimate and two Newton steps (x > 0; a sqrt and a division in double are some fifty instructions)
-__device__ __forceinline__ double rsqrt_full(double x) {
-    const bool tiny = x < 0x1p-900;
-    const double xs = tiny ? x * 0x1p+200 : x;
-    double y = __builtin_amdgcn_rsq(xs);
-    const double h = 0.5 * xs;
-    y = __builtin_fma(y, __builtin_fma(-h * y, y, 0.5), y);
-    y = __builtin_fma(y, __builtin_fma(-h * y, y, 0.5), y);
-    return tiny ? y * 0x1p+100 : y;
-}
-
 // =====================================================================================================
 // ROW kernels: transforms along x over the Sh SLM rows.
 //   MODE 0 : phase -> G            (_build_nearfield :1000 + row half of fft2 :1048)
@@ -697,7 +741,7 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                             const unsigned co = c_off + (unsigned)m * c_step;
                             R p = M::atan2(v[m].y * sc, v[m].x * sc) - bkn.template ld<R>(co, 0u);   // (no kernel: reads 0)
                             bph.template st<R>(p, co, 0u);
-                            if constexpr (m % AT_GROUP == AT_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
+                            sched_fence_every<m, AT_GROUP>();
                         });
                     }
                 }
@@ -726,7 +770,7 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                         nf = mk<R>(amv * sgs * cs, amv * sgs * sn);
                     }
                     v[m] = nf;
-                    if constexpr (m % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+                    sched_fence_every<m, 4>();
                 });
                 HGS_T(fft.tr_n, 3);
                 fft.fwd(v, lds, j);
@@ -852,7 +896,7 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                             ph[c] = p;
                         }
                     }
-                    if constexpr (m % AT_GROUP == AT_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
+                    sched_fence_every<m, AT_GROUP>();
                 });
             }
         }
@@ -892,7 +936,7 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                     }
                 }
                 v[m] = nf;
-                if constexpr (m % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+                sched_fence_every<m, 4>();
             });
             HGS_T(fft.tr_n, 3);
             if constexpr (NS < 16) fft.template fwd_lead<NS>(v, lds, j);
@@ -950,12 +994,7 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
         }
     }
 #if HGS_TRACE
-    __syncthreads();
-    if (a.nf_out != nullptr && MODE == 2) {   // the microbenchmark passes its dump buffer through nf_out
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(a.nf_out) + (size_t)blockIdx.x * 512;
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + HGS_TRACE_OFF);
-        for (int i = tid; i < 512; i += blockDim.x) dst[i] = src[i];
-    }
+    if (a.nf_out != nullptr && MODE == 2) trace_dump(a.nf_out, 512);   // the microbenchmark passes its dump buffer through nf_out
 #endif
 }
 
@@ -1451,18 +1490,15 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
             if (do_upd) {
                 const R t = tr[m];
                 if (RULE == 1 || cp.method == M_LEONARDO || cp.method == M_KIM) {
-                    // evaluated for every lane and selected (a branch per pixel splits the pass into 16 blocks):
-                    // T == 0 -> factor 1 (:1841); inf (:1840,:1867) and nan (:1843) -> 1
-                    // (fp64: the rule is some hundred instructions of double log2 / exp2 -- worth the branch)
+                    // (fp64: the rule is some hundred instructions of double log2 / exp2 -- worth a branch per pixel)
                     if (sizeof(R) == 4 || t != (R)0) {
-                        R fc = leonardo_factor<R>(p2, t, cp.inv_fnorm, cp.p_exp);
-                        fc = (t != (R)0 && fc < (R)INFINITY) ? fc : (R)1;
+                        const R fc = leonardo_guarded<R>(p2, t, cp.inv_fnorm, cp.p_exp);
                         wv *= fc;
                     }
                 } else {
                     wv *= weight_factor<R>(cp.method, M::sqrt(p2) * cp.inv_fnorm, t, cp.p_exp, cp.p_fac, nogv);
                 }
-                if (is_nan(wv)) wv = (R)0.0001;            // :1873
+                wv = nan_floor(wv);
                 if (x_presum) {                            // pre-pass: what this update adds to sum w^2 -- nothing is kept,
                     const double w0 = (double)wraw * (double)wsc;      // nothing rebuilt (float64: the phasor alone is a double rsqrt)
                     acc_w += (R)((double)wv * (double)wv - w0 * w0);   // (each term in double; a lane adds a few hundred of them)
@@ -1483,14 +1519,14 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
             if constexpr (PHASE == 2) {
                 if constexpr (PF_AHEAD) {
                     const float4 qv = (m / 4 == 0) ? pfq0 : (m / 4 == 1) ? pfq1 : (m / 4 == 2) ? pfq2 : pfq3;
-                    M::sincos_phase((R)((m % 4 == 0) ? qv.x : (m % 4 == 1) ? qv.y : (m % 4 == 2) ? qv.z : qv.w), &si, &co);
+                    M::sincos_phase((R)quad_at<m>(qv), &si, &co);
                 }
                 else M::sincos_phase(pfc[idx], &si, &co);
             } else {
-                if (sizeof(R) == 4 || p2 > (R)0) {         // exp(i*atan2(F)) == F/|F|; atan2(0,0) = 0 (quirk A6)
-                    const R inv = rsqrt_full(p2);
-                    co = (p2 > (R)0) ? F.x * inv : (R)1;
-                    si = (p2 > (R)0) ? F.y * inv : (R)0;
+                if (sizeof(R) == 4 || p2 > (R)0) {         // (fp64: the double rsqrt is worth a branch)
+                    const Cx<R> ph = unit_phasor(F, p2);
+                    co = ph.x;
+                    si = ph.y;
                 } else {
                     co = 1;
                     si = 0;
@@ -1526,7 +1562,7 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
             HGS_T(fft.tr_n, 40 + m);
 #endif
             // (fp64: one pixel at a time -- four interleaved double atan2 / sincos / log2 chains cost 100+ registers)
-            if constexpr (m % (sizeof(R) == 4 ? HGS_CONS_GROUP : HGS_CONS_GROUP_F64) == (sizeof(R) == 4 ? HGS_CONS_GROUP : HGS_CONS_GROUP_F64) - 1) __builtin_amdgcn_sched_barrier(0);
+            sched_fence_every<m, (sizeof(R) == 4 ? HGS_CONS_GROUP : HGS_CONS_GROUP_F64)>();
         };
         if constexpr (!LEAN) {
             static_for<0, 16>(cons);
@@ -1589,13 +1625,7 @@ __global__ __launch_bounds__(ColCfg<N>::WG, HGS_FUSED_OCC) void col_fused_kernel
         if (tid == 0) a.wpartial[(size_t)b * gridDim.x + blockIdx.x] = s;
     }
 #if HGS_TRACE
-    __syncthreads();
-    {   // dump this workgroup's events (128 per wave) through fpartial
-        const int nev = ((int)blockDim.x >> 6) * 128;
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(a.fpartial) + (size_t)blockIdx.x * nev;
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + HGS_TRACE_OFF);
-        for (int i = tid; i < nev; i += blockDim.x) dst[i] = src[i];
-    }
+    trace_dump(a.fpartial, ((int)blockDim.x >> 6) * 128);     // (fpartial doubles as the destination in the microbenchmarks)
 #endif
 }
 
@@ -1949,12 +1979,7 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
             static_for<0, 16>([&](auto m_) {
                 constexpr int m = m_;
                 const unsigned idx = lane_pos<T>(j, m);
-                // Sparse targets (spot arrays): where weight and target are both zero the rule leaves the
-                // weight at zero (T == 0 -> factor 1, :1841) and the constrained field is w * e^{i phi} = 0.
-                // Skip the arithmetic when that holds for the whole wave (not when phase_ff or amp_ff of
-                // every pixel must be produced).
-                if (PHASE != 1 && !(STATS && (a.do_stats & 2)) &&
-                    __builtin_amdgcn_ballot_w64(wr[m] != (R)0 || tr[m] != (R)0) == 0) {
+                if (PHASE != 1 && !(STATS && (a.do_stats & 2)) && wave_all_zero(wr[m], tr[m])) {
                     v[m] = mk<R>(0, 0);
                     if constexpr (SPLIT) park[m * T + j] = mk<R>(0, 0);
                     if (EXTRAS && !FIXED && cp.nog_pass) acc_w += (R)1;          // T == 0 -> fc = 1 (:1841)
@@ -1972,13 +1997,12 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
                 if (do_upd) {
                     const R t = tr[m];
                     if (RULE == 1 || FIXED || cp.method == M_LEONARDO || cp.method == M_KIM) {
-                        R fc = leonardo_factor<R>(p2, t, cp.inv_fnorm, cp.p_exp);     // (eager + select, see col_fused_kernel)
-                        fc = (t != (R)0 && fc < (R)INFINITY) ? fc : (R)1;
+                        const R fc = leonardo_guarded<R>(p2, t, cp.inv_fnorm, cp.p_exp);
                         wv *= fc;
                     } else {
                         wv *= weight_factor<R>(cp.method, M::sqrt(p2) * cp.inv_fnorm, t, cp.p_exp, cp.p_fac, nogv);
                     }
-                    if (is_nan(wv)) wv = (R)0.0001;
+                    wv = nan_floor(wv);
                     w_changed |= (wv != wraw);                 // stored after the loop, 64 contiguous bytes per lane
                     wr[m] = wv;
                     acc_w += wv * wv;
@@ -1994,10 +2018,7 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
                     M::sincos_phase(pf[m], &sn, &cs);
                     ph = mk<R>(cs, sn);
                 } else {
-                    {
-                        const R inv = rsqrt_full(p2);
-                        ph = mk<R>((p2 > (R)0) ? F.x * inv : (R)1, (p2 > (R)0) ? F.y * inv : (R)0);
-                    }
+                    ph = unit_phasor(F, p2);
                     if constexpr (PHASE == 1) pf[m] = M::atan2(F.y, F.x);
                 }
                 // ff = wv * ph; inverse-transform input = (-1)^k * ff * conj(shift factor)
@@ -2023,13 +2044,8 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
                 } else if constexpr (SPLIT) {
                     park[m * T + j] = mk<R>(0, 0);
                 }
-                // PHASE 1: the stored phase leaves four pixels (16 contiguous bytes) at a time -- sixteen of them kept until
-                // after the loop put the 4096 / 8192-point RULE 1 instances 12 / 8 registers over their 256
-                if constexpr (PHASE == 1 && m % 4 == 3) {
-                    static_for<m - 3, m + 1>([&](auto i_) { constexpr int i = i_; pfc[lane_pos<T>(j, i)] = pf[i]; });
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (m % (sizeof(R) == 4 ? HGS_CONS_GROUP : 4) == (sizeof(R) == 4 ? HGS_CONS_GROUP : 4) - 1) __builtin_amdgcn_sched_barrier(0);
+                if constexpr (PHASE == 1 && m % 4 == 3) store_phase_quad<T, m>(pfc, j, pf[m - 3], pf[m - 2], pf[m - 1], pf[m]);
+                sched_fence_every<m, (sizeof(R) == 4 ? HGS_CONS_GROUP : 4)>();
             });
             if constexpr (SPLIT) { if (noise_any) *nflag = 1; }
             if constexpr (STATS) sacc.flush(stat_slot);
@@ -2122,13 +2138,7 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_tile_kernel(ColArgs
         if (j == 0) a.wpartial[(size_t)b * gridDim.x + blockIdx.x] = s;
     }
 #if HGS_TRACE
-    __syncthreads();
-    {   // dump this workgroup's events (128 per wave): fpartial doubles as the destination in the microbenchmark
-        const int nev = ((int)blockDim.x >> 6) * 128;
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(a.fpartial) + (size_t)blockIdx.x * nev;
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + HGS_TRACE_OFF);
-        for (int i = j; i < nev; i += blockDim.x) dst[i] = src[i];
-    }
+    trace_dump(a.fpartial, ((int)blockDim.x >> 6) * 128);     // (fpartial doubles as the destination in the microbenchmarks)
 #endif
 }
 
@@ -2266,13 +2276,11 @@ __global__ __launch_bounds__(N / 16, HGS_FUSED_OCC) void col_presum_kernel(ColAr
             const Cx<R> F = cmul(v[m], om);
             const R p2 = F.x * F.x + F.y * F.y;
             const R w0 = wr[m] * wsc;
-            R fc = leonardo_factor<R>(p2, t, cp.inv_fnorm, cp.p_exp);
-            fc = (t != (R)0 && fc < (R)INFINITY) ? fc : (R)1;
-            R w1 = w0 * fc;
-            if (is_nan(w1)) w1 = (R)0.0001;
+            const R fc = leonardo_guarded<R>(p2, t, cp.inv_fnorm, cp.p_exp);
+            const R w1 = nan_floor(w0 * fc);
             // (w0 NaN -- weights nobody has updated yet -- cannot occur: the engine takes this path only behind an update)
             acc += (double)w1 * (double)w1 - (double)w0 * (double)w0;
-            if constexpr (m % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+            sched_fence_every<m, 4>();
         });
         // (consecutive forward transforms need no extra rendezvous: the first exchange of the next one is wave-local, in the
         //  wave's own regions, and this one ended with the barrier behind its cross-wave gather -- as between the columns of
@@ -2501,10 +2509,9 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 if constexpr (PFQ) {
                     const float4 qv = ((m / 4) & 1) ? qb : qa;
                     // (pixels 4-7 read qb = pq[1], 8-11 qa = pq[2], 12-15 qb = pq[3])
-                    pfm = (m % 4 == 0) ? qv.x : (m % 4 == 1) ? qv.y : (m % 4 == 2) ? qv.z : qv.w;
+                    pfm = quad_at<m>(qv);
                 }
-                // wave-uniform skip where weight and target are zero (see col_tile_kernel)
-                if (PHASE != 1 && __builtin_amdgcn_ballot_w64(wr[m] != (R)0 || tr[m] != (R)0) == 0) {
+                if (PHASE != 1 && wave_all_zero(wr[m], tr[m])) {
                     v[m] = mk<R>(0, 0);
                     return;
                 }
@@ -2514,10 +2521,9 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 R wv = wraw * wsc;
                 if constexpr (do_upd) {
                     const R t = tr[m];
-                    R fc = leonardo_factor<R>(p2, t, cp.inv_fnorm, cp.p_exp);
-                    fc = (t != (R)0 && fc < (R)INFINITY) ? fc : (R)1;
+                    const R fc = leonardo_guarded<R>(p2, t, cp.inv_fnorm, cp.p_exp);
                     wv *= fc;
-                    if (is_nan(wv)) wv = (R)0.0001;
+                    wv = nan_floor(wv);
                     w_changed |= (wv != wraw);
                     wr[m] = wv;
                     acc_w += wv * wv;
@@ -2528,16 +2534,12 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                     M::sincos_phase(pfm, &sn, &cs);
                     ph = mk<R>(cs, sn);
                 } else {
-                    const R inv = rsqrt_full(p2);
-                    ph = mk<R>((p2 > (R)0) ? F.x * inv : (R)1, (p2 > (R)0) ? F.y * inv : (R)0);
+                    ph = unit_phasor(F, p2);
                     if constexpr (PHASE == 1) pf[m] = M::atan2(F.y, F.x);
                 }
                 v[m] = cmulc(ph, om) * wv;
-                if constexpr (PHASE == 1 && m % 4 == 3) {
-                    static_for<m - 3, m + 1>([&](auto i_) { constexpr int i = i_; pfc[lane_pos<T>(j, i)] = pf[i]; });
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (m % TILE2_CONS_GROUP == TILE2_CONS_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
+                if constexpr (PHASE == 1 && m % 4 == 3) store_phase_quad<T, m>(pfc, j, pf[m - 3], pf[m - 2], pf[m - 1], pf[m]);
+                sched_fence_every<m, TILE2_CONS_GROUP>();
             });
             if (do_upd && w_changed) {
                 static_for<0, 16>([&](auto m_) { constexpr int m = m_; wc[lane_pos<T>(j, m)] = wr[m]; });
@@ -2623,13 +2625,7 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
         if (tid == 0) a.wpartial[(size_t)b * gridDim.x + blockIdx.x] = s;
     }
 #if HGS_TRACE
-    __syncthreads();
-    {   // dump this workgroup's events (128 per wave): fpartial doubles as the destination in the microbenchmark
-        const int nev = ((int)blockDim.x >> 6) * 128;
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(a.fpartial) + (size_t)blockIdx.x * nev;
-        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(smem + HGS_TRACE_OFF);
-        for (int i = tid; i < nev; i += blockDim.x) dst[i] = src[i];
-    }
+    trace_dump(a.fpartial, ((int)blockDim.x >> 6) * 128);     // (fpartial doubles as the destination in the microbenchmarks)
 #endif
 }
 
@@ -2682,8 +2678,7 @@ template <typename R> __global__ void ew_weight_update(EwArgs<R> a) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.P; i += (size_t)gridDim.x * blockDim.x) {
         const size_t idx = (size_t)b * a.P + i;
         const R fc = weight_factor<R>(a.cp.method, a.amp_ff[idx] * inv_fn, a.t[idx], a.cp.p_exp, a.cp.p_fac, nog);
-        R wv = a.w[idx] * fc;
-        if (is_nan(wv)) wv = (R)0.0001;
+        const R wv = nan_floor(a.w[idx] * fc);
         a.w[idx] = wv;
         acc += (double)wv * (double)wv;
     }
@@ -2916,8 +2911,7 @@ template <typename R> __global__ void spot_update(SpotArgs<R> a) {
         const size_t idx = (size_t)b * P + (size_t)kx * a.g.Ph + col_pos(ky, a.g.lane_T);
         const R f = (a.feedback == 2) ? (R)a.ext_amp[n] : a.fb[(size_t)b * N + n];
         const R fc = weight_factor<R>(a.cp.method, f * inv_fn, (R)a.spot_amp[n], a.cp.p_exp, a.cp.p_fac, nog);
-        R wv = a.w[idx] * fc;
-        if (is_nan(wv)) wv = (R)0.0001;
+        const R wv = nan_floor(a.w[idx] * fc);
         a.w[idx] = wv;
         acc += (double)wv * (double)wv;
     }
