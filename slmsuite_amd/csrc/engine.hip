@@ -5,7 +5,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,13 +12,12 @@
 #include <vector>
 
 #include "../../include/hgs.h"
+#include "hgs_error.hpp"
 #include "launch.hpp"
 #include "column_plan.hpp"
 #include "devbuf.hpp"
 #include "engine_state.hpp"
-#include "compressed_kernels.hpp"
-#include "cgemm.hpp"
-#include "compressed_sep.hpp"
+#include "compressed_backend.hpp"
 #include "bluestein.hpp"
 #include "cg_kernels.hpp"
 #include "vortex_kernels.hpp"
@@ -27,30 +25,6 @@
 #include <dlfcn.h>
 
 namespace hgs {
-
-static thread_local std::string g_err;
-static int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-#define HIPCHK(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(HGS_ERR_DEVICE, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-#define LCHK(x)                                                                                \
-    do {                                                                                       \
-        int e_ = (x);                                                                          \
-        if (e_ != 0)                                                                           \
-            return fail(HGS_ERR_DEVICE, "kernel launch failed: %s (%s:%d)",                    \
-                        hipGetErrorString((hipError_t)e_), __FILE__, __LINE__);                \
-    } while (0)
 
 // roctx ranges around the operators (HGS_OPT_ROCTX): resolved at run time so that the library keeps its single
 // link dependency (libamdhip64); rocprofv3 --marker-trace shows them.  librocprofiler-sdk-roctx first (rocprofv3),
@@ -224,9 +198,6 @@ template <typename R> struct Engine : EngineBase {
     // engine policy (hgs_set_option) and the developer switches, read from the environment once, in init() (read_tuning)
     Tuning tun;
     int opt_stepwise = 0;                  // HGS_OPT_FORCE_STEPWISE
-    int opt_separable = 1;                 // HGS_OPT_SEPARABLE
-    int opt_sep_min = 96;                  // smallest spot count the matrix-core form is used for (tools/sep_crossover.py)
-    int opt_sep_wg = 0;                    // HGS_OPT_SEP_WORKGROUPS: cap on the workgroups of each stream-K GEMM (0 = 2 * #CU)
     int opt_roctx = 0;                     // HGS_OPT_ROCTX: roctx ranges around the operators
     // what the buffers currently hold (G left behind, farfield, phase_ff, the weights' norm, the column lists): engine_state.hpp
     EngineState state;
@@ -267,42 +238,10 @@ template <typename R> struct Engine : EngineBase {
     DevBuf<C> blue_tab[2][2][3];       // [x|y][forward|inverse][A, Bf, Cc]
     DevBuf<C> blue_tw_own[2];          // equal convolution lengths share one table: blue_tw[1] is blue_tw[0] then
     C* blue_tw[2] = {nullptr, nullptr};
-    // kind 1 (compressed)
-    DevBuf<R> xg, yg, coeff, ext_r;
-    DevBuf<int> mono;
-    DevBuf<Cx<R>> cpartial;
-    DevBuf<double> cnorm;
-    int c_nblocks = 0, c_degree = -1, c_rows = 0;
-    // separable (matrix-core) form of the compressed transforms, fp32 only (compressed_sep.hpp)
-    bool grid_sep[2] = {false, false}, c_sep = false;
-    std::vector<double> xs_host, ys_host;
-    DevBuf<double> sep_c;        // [2][SEP_MAXDEG+1][N] polynomial coefficients of fx_n, fy_n
-    DevBuf<double> sep_g;        // xs[W] then ys[H]
-    DevBuf<float2> sep_ex;       // [N][W]
-    DevBuf<float2> sep_exT;      // [W][N]
-    DevBuf<float2> sep_ey;       // [N][H]
-    DevBuf<float2> sep_nfT;      // [B][W][H]
-    DevBuf<float2> sep_b2;       // [B][N][H]
-    DevBuf<float2> sep_c1;       // [B][tiles_n1 * 2 * split1][Np] partial y contractions of the n2f GEMM epilogue
-    DevBuf<float2> sep_c2;       // [B][split2][H][W]
-    DevBuf<double> sep_norm;     // [B][ceil(N/4)]
-    int sep_split1 = 1, sep_kper1 = 0, sep_split2 = 1, sep_kper2 = 0, sep_degx = 0, sep_degy = 0;
-    // stream-K schedule of the two GEMMs (cgemm_streamk): sep_split1 / sep_split2 are then the partial planes of C
-    unsigned sk_flag1 = 0, sk_flag2 = 0;   // DF_SK_CAP where the option holds G below min(2 * #CU, steps)
-    int sk_G1 = 0, sk_G2 = 0, sk_kt1 = 0, sk_kt2 = 0, sk_tm1 = 0, sk_tn1 = 0, sk_tm2 = 0, sk_tn2 = 0;
-    DevBuf<int> sk_tab;          // [first_wg 1][nseg 1][first_wg 2][nseg 2]
-    int sep_Np = 0, sep_Hp = 0, sep_Wp = 0, sep_Wk = 0, sep_Nk = 0;   // padded leading dimensions / row counts
-    std::vector<int32_t> mono_host;
-    std::vector<R> coeff_host;
-    bool has_grid[2] = {false, false}, has_mono = false, has_coeff = false;
-    // run kernels of the direct compressed transforms (compressed_kernels.hpp: regular grid, degree <= 2, fp32)
-    bool run_ok = false;
-    int opt_run = 1;                       // HGS_OPT_RUN_KERNELS
-    DevBuf<CRunRec> run_rec;            // [N]
-    DevBuf<double> run_ys;              // [H]
-    DevBuf<Cx<float>> run_nf;           // [B][run_chunks][S]
-    double run_x0 = 0, run_hx = 0;
-    int run_rpr = 0, run_blocks = 0, run_chunks = 1, run_nper = 0, run_nf_chunks = 0;
+    // kind 1 (compressed): the uploaded problem, the tables of its kernel forms and their launches (compressed_backend.hpp);
+    // ext_r: the external feedback amplitudes, converted for the constraint kernels
+    CompressedBackend<R> comp;
+    DevBuf<R> ext_r;
     // host state
     double amp_scalar = 0, amp_norm2 = 1.0;
     bool has_amp = false, has_kern = false, has_target = false, has_spots = false;
@@ -670,6 +609,11 @@ template <typename R> struct Engine : EngineBase {
         });
     }
 
+    // ---- kind 1: CompressedSpotHologram (the transforms themselves: compressed_backend.hpp) -------
+    CompressedView<R> cview() const {
+        return {stream, B, S, P, g, n_cu, phase.get(), has_amp ? amp.get() : nullptr, has_kern ? kern.get() : nullptr, amp_scalar,
+                ff.get(), aff.get(), sums.get()};
+    }
     int init_compressed(const hgs_config& c) {
         if (c.n_spots < 1 || c.n_monomials < 1 || c.slm_h < 1 || c.slm_w < 1 || c.batch < 1)
             return fail(HGS_ERR_ARG, "compressed engine needs n_spots, n_monomials, slm shape and batch >= 1");
@@ -679,296 +623,17 @@ template <typename R> struct Engine : EngineBase {
         S = (size_t)g.Sh * g.Sw;
         P = (size_t)c.n_spots;
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        c_nblocks = (int)((S + (size_t)C_WG * C_PT - 1) / ((size_t)C_WG * C_PT));
         col_blocks = 1; tile_blocks = 1; row_blocks = 1;
         ew_blocks = (int)std::min<size_t>((P + 255) / 256, (size_t)std::max(1, n_cu * 8 / B));
-        c_rows = std::max(6, c.n_monomials);
-        run_rpr = (g.Sw + CR_RUN - 1) / CR_RUN;
-        run_blocks = (g.Sh * run_rpr + 63) / 64;
-        if (dalloc(phase, B * S) || dalloc(w, B * P) || dalloc(t, B * P) || dalloc(xg, S) || dalloc(yg, S) ||
-            dalloc(mono, (size_t)2 * c.n_monomials) || dalloc(coeff, (size_t)c_rows * P) ||
-            dalloc(cpartial, (size_t)B * std::max(c_nblocks, run_blocks) * P) ||
-            dalloc(cnorm, (size_t)B * ((P + C_RED_SPOTS - 1) / C_RED_SPOTS)) || dalloc(ext_amp, P) || dalloc(ext_r, B * P)) return HGS_ERR_DEVICE;
+        if (dalloc(phase, B * S) || dalloc(w, B * P) || dalloc(t, B * P)) return HGS_ERR_DEVICE;
+        if (int e = comp.init(cview(), c.n_spots, c.n_monomials, tun.mono_tab)) return e;
+        if (dalloc(ext_amp, P) || dalloc(ext_r, B * P)) return HGS_ERR_DEVICE;
         if (int e = alloc_partials((size_t)B, (size_t)B)) return e;
         HIPCHK(hipStreamSynchronize(stream));
         return 0;
     }
-
-    // repack the monomial weights for the degree-specialised kernels (canonical [1,x,y,x2,xy,y2])
-    int pack_coeff() {
-        if (!has_mono || !has_coeff) return 0;
-        const int M = cfg.n_monomials, N = cfg.n_spots;
-        c_degree = 0;
-        for (int m = 0; m < M; ++m) c_degree = std::max(c_degree, mono_host[2 * m] + mono_host[2 * m + 1]);
-        for (int m = 0; m < M; ++m) {
-            const int px = mono_host[2 * m], py = mono_host[2 * m + 1];
-            if (px == -1 && py == 0) { c_degree = std::max(c_degree, 3); continue; }   // vortex plate: general kernels
-            if (px < 0 || py < 0)
-                return fail(HGS_ERR_ARG, "unrecognized term (%d, %d): the only pseudo-term is the vortex plate (-1, 0)", px, py);
-        }
-        if (c_degree <= 2) {
-            std::vector<R> c6((size_t)6 * N, (R)0);
-            for (int m = 0; m < M; ++m) {
-                const int px = mono_host[2 * m], py = mono_host[2 * m + 1];
-                const int slot = (px == 0 && py == 0) ? 0 : (px == 1 && py == 0) ? 1 : (px == 0 && py == 1) ? 2
-                                 : (px == 2) ? 3 : (px == 1) ? 4 : 5;
-                for (int n = 0; n < N; ++n) c6[(size_t)slot * N + n] += coeff_host[(size_t)m * N + n];
-            }
-            if (int e_ = h2d(coeff, c6.data(), c6.size() * sizeof(R))) return e_;
-        } else {
-            if (int e_ = h2d(coeff, coeff_host.data(), (size_t)M * N * sizeof(R))) return e_;
-        }
-        return sep_refresh();
-    }
-
-    // ---- separable / matrix-core form (compressed_sep.hpp) ----
-    // split-K factor: fill the 2 * n_cu resident workgroups of cgemm_kouter in whole rounds (a 128 x 128
-    // output grid rarely does by itself: 711 tiles = 1.39 rounds, 135 tiles = 0.26), smallest such split
-    static void split_for(int tiles, int K, int n_cu, int* split, int* k_per) {
-        const int slots = 2 * n_cu;
-        int best = 1;
-        double best_eff = 0;
-        for (int sp = 1; sp <= 32 && K / sp >= 128; ++sp) {
-            const int w = tiles * sp;
-            const double eff = (double)w / ((double)((w + slots - 1) / slots) * slots);
-            if (eff > best_eff + 0.08) { best_eff = eff; best = sp; }   // partial tiles cost traffic: need a real gain
-        }
-        int kp = ((K + best - 1) / best + CG_BK - 1) / CG_BK * CG_BK;
-        *split = (K + kp - 1) / kp;
-        *k_per = kp;
-    }
-    // called whenever the grids, the term set or the coefficients changed
-    int sep_refresh() {
-        if (int e = sep_refresh_impl()) return e;
-        return run_refresh();
-    }
-    // Run kernels: x must be a regular grid over the columns (checked against the uploaded values), y a function of the
-    // row, the polynomial of degree <= 2.  Per spot: canonical coefficients in double and the constant factor of the
-    // recurrence (degree 2: C_n = exp(i 2 c3 h^2); degree 1: D_n = exp(i c1 h)).
-    int run_refresh() {
-        run_ok = false;
-        if constexpr (sizeof(R) != 4) return 0;
-        if (cfg.kind != 1) return 0;
-        if (!(has_grid[0] && has_grid[1] && grid_sep[0] && grid_sep[1] && has_mono && has_coeff)) return 0;
-        if (c_degree < 0 || c_degree > 2) return 0;
-        const int M = cfg.n_monomials, N = cfg.n_spots, H = g.Sh, W = g.Sw;
-        if (W < 2) return 0;
-        const double x0 = xs_host[0], hx = (xs_host[W - 1] - x0) / (double)(W - 1);
-        double xmax = 0;
-        for (int x = 0; x < W; ++x) xmax = std::max(xmax, std::fabs(xs_host[x]));
-        // the uploaded values are fp32 roundings of the grid: half an ulp of the largest coordinate each
-        for (int x = 0; x < W; ++x)
-            if (std::fabs(xs_host[x] - (x0 + x * hx)) > 2.5e-7 * xmax + 1e-30) return 0;
-        std::vector<CRunRec> rec((size_t)N);
-        for (int n = 0; n < N; ++n) {
-            CRunRec& r = rec[n];
-            for (double& c : r.c) c = 0;
-            for (int m = 0; m < M; ++m) {
-                const int px = mono_host[2 * m], py = mono_host[2 * m + 1];
-                const int slot = (px == 0 && py == 0) ? 0 : (px == 1 && py == 0) ? 1 : (px == 0 && py == 1) ? 2
-                                 : (px == 2) ? 3 : (px == 1) ? 4 : 5;
-                r.c[slot] += (double)coeff_host[(size_t)m * N + n];
-            }
-            const double ang = c_degree == 2 ? 2.0 * r.c[3] * hx * hx : r.c[1] * hx;
-            r.cr = (float)std::cos(ang);
-            r.ci = (float)std::sin(ang);
-            r.pad0 = r.pad1 = 0;
-        }
-        HIPCHK(run_rec.ensure((size_t)N));
-        HIPCHK(run_ys.ensure((size_t)H));
-        if (int e_ = h2d(run_rec, rec.data(), rec.size() * sizeof(CRunRec))) return e_;
-        if (int e_ = h2d(run_ys, ys_host.data(), (size_t)H * sizeof(double))) return e_;
-        run_x0 = x0;
-        run_hx = hx;
-        // spot chunks (grid.z): about eight waves per SIMD, whole groups of 64 spots
-        int want = std::max(1, (8 * 4 * n_cu + run_blocks - 1) / run_blocks);
-        want = std::min(want, 8);
-        run_nper = std::max(64, ((N + want - 1) / want + 63) / 64 * 64);
-        run_chunks = (N + run_nper - 1) / run_nper;
-        run_ok = true;
-        return 0;
-    }
-    bool use_run() const { return run_ok && opt_run; }
-    unsigned bflag() const { return B > 1 ? DF_BATCH : 0u; }
-    CRunArgs run_args(const CArgs<R>& a) {
-        CRunArgs ra{};
-        if constexpr (sizeof(R) == 4) ra.a = a;
-        ra.a.nblocks = run_blocks;
-        ra.rec = run_rec; ra.ys = run_ys; ra.x0 = run_x0; ra.hx = run_hx; ra.H = g.Sh; ra.W = g.Sw; ra.rpr = run_rpr;
-        ra.n_per = run_nper; ra.nf_part = run_nf;
-        return ra;
-    }
-    int run_n2f(CArgs<R>& a) {
-        CRunArgs ra = run_args(a);
-        a.nblocks = run_blocks;                       // what c_n2f_reduce sums over
-        const dim3 grid(run_blocks, B, run_chunks);
-        if (c_degree <= 1) { dispatch_note(dispatch_site<KCn2fRun, float, 1>(), bflag()); hipLaunchKernelGGL((c_n2f_run<1>), grid, dim3(64), 0, stream, ra); }
-        else { dispatch_note(dispatch_site<KCn2fRun, float, 2>(), bflag()); hipLaunchKernelGGL((c_n2f_run<2>), grid, dim3(64), 0, stream, ra); }
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    int run_f2n(const CArgs<R>& a) {
-        if (!run_nf || run_nf_chunks < run_chunks) {
-            HIPCHK(run_nf.release(stream));
-            HIPCHK(run_nf.alloc((size_t)B * run_chunks * S));
-            run_nf_chunks = run_chunks;
-        }
-        CRunArgs ra = run_args(a);
-        const dim3 grid(run_blocks, B, run_chunks);
-        if (c_degree <= 1) { dispatch_note(dispatch_site<KCf2nRun, float, 1>(), bflag()); hipLaunchKernelGGL((c_f2n_run<1>), grid, dim3(64), 0, stream, ra); }
-        else { dispatch_note(dispatch_site<KCf2nRun, float, 2>(), bflag()); hipLaunchKernelGGL((c_f2n_run<2>), grid, dim3(64), 0, stream, ra); }
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(c_f2n_run_finish, dim3((unsigned)((S + 255) / 256), B), dim3(256), 0, stream, ra.a,
-                           (const Cx<float>*)run_nf, run_chunks);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    // stream-K: the (tile, k tile) steps of each GEMM in G = min(HGS_OPT_SEP_WORKGROUPS or 2 * #CU, 2 * #CU, steps) equal shares
-    // (at most one workgroup per step: every workgroup owns work, the owners of a tile are consecutive); per tile the first
-    // workgroup and the number of partial planes it is spread over (consumers add exactly those), and the two buffers of
-    // partial results, whose size follows the planes.  Called when the tables are first made and when the option changes.
-    int sk_retable() {
-        const int H = g.Sh, W = g.Sw;
-        const int t1 = sk_tm1 * sk_tn1, t2 = sk_tm2 * sk_tn2;
-        const long long full = 2 * n_cu, want = opt_sep_wg > 0 ? std::min<long long>(opt_sep_wg, full) : full;
-        const long long steps1 = (long long)t1 * sk_kt1, steps2 = (long long)t2 * sk_kt2;
-        sk_G1 = (int)std::min(want, steps1);
-        sk_G2 = (int)std::min(want, steps2);
-        sk_flag1 = sk_G1 < std::min(full, steps1) ? DF_SK_CAP : 0u;
-        sk_flag2 = sk_G2 < std::min(full, steps2) ? DF_SK_CAP : 0u;
-        std::vector<int> tab((size_t)2 * (t1 + t2));
-        sep_split1 = sk_fill(t1, sk_kt1, sk_G1, tab.data(), tab.data() + t1);
-        sep_split2 = sk_fill(t2, sk_kt2, sk_G2, tab.data() + 2 * t1, tab.data() + 2 * t1 + t2);
-        // (launches on the stream may still read what a change of the option replaces)
-        HIPCHK(sk_tab.release(stream));
-        HIPCHK(sep_c1.release(stream));
-        HIPCHK(sep_c2.release(stream));
-        HIPCHK(sk_tab.alloc(tab.size()));
-        if (int e_ = h2d(sk_tab, tab.data(), tab.size() * sizeof(int))) return e_;
-        HIPCHK(sep_c1.alloc(sk_part_elems(B, sk_tn1, sep_split1, (size_t)sep_Np)));
-        HIPCHK(sep_c2.alloc(sk_c_elems(B, sep_split2, (size_t)H, (size_t)W)));
-        return 0;
-    }
-    int sep_refresh_impl() {
-        c_sep = false;
-        if (sizeof(R) != 4 || cfg.kind != 1) return 0;
-        if (!(has_grid[0] && has_grid[1] && grid_sep[0] && grid_sep[1] && has_mono && has_coeff)) return 0;
-        const int M = cfg.n_monomials, N = cfg.n_spots, H = g.Sh, W = g.Sw;
-        int dx = 0, dy = 0;
-        for (int m = 0; m < M; ++m) {
-            const int px = mono_host[2 * m], py = mono_host[2 * m + 1];
-            if (px < 0 || py < 0 || (px > 0 && py > 0) || px > SEP_MAXDEG || py > SEP_MAXDEG) return 0;   // not separable
-            dx = std::max(dx, px);
-            dy = std::max(dy, py);
-        }
-        std::vector<double> c((size_t)2 * (SEP_MAXDEG + 1) * N, 0.0);
-        for (int m = 0; m < M; ++m) {
-            const int px = mono_host[2 * m], py = mono_host[2 * m + 1];
-            double* dst = (py == 0) ? &c[(size_t)px * N] : &c[((size_t)(SEP_MAXDEG + 1) + py) * N];
-            for (int n = 0; n < N; ++n) dst[n] += (double)coeff_host[(size_t)m * N + n];
-        }
-        if (!sep_c) {
-            // operands of the matrix-core GEMM are padded to whole tiles (zero filled once, never rewritten)
-            auto up = [](int v, int q) { return (v + q - 1) / q * q; };
-            sk_tm1 = (N + CG_BM - 1) / CG_BM; sk_tn1 = (H + CG_BN - 1) / CG_BN; sk_kt1 = (W + CG_BK - 1) / CG_BK;
-            sk_tm2 = (H + CG_BM - 1) / CG_BM; sk_tn2 = (W + CG_BN - 1) / CG_BN; sk_kt2 = (N + CG_BK - 1) / CG_BK;
-            sep_Np = up(N, CG_BM); sep_Hp = up(H, CG_BN); sep_Wp = up(W, CG_BN);
-            if (int e_ = sk_retable()) return e_;
-            sep_Wk = sk_kt1 * CG_BK;
-            sep_Nk = sk_kt2 * CG_BK;
-            HIPCHK(sep_c.alloc(c.size()));
-            HIPCHK(sep_g.alloc((size_t)(W + H)));
-            if (dalloc(sep_ex, (size_t)sep_Nk * sep_Wp)) return HGS_ERR_DEVICE;       // [Nk][Wp]  (B of the f2n GEMM)
-            if (dalloc(sep_exT, (size_t)sep_Wk * sep_Np)) return HGS_ERR_DEVICE;      // [Wk][Np]  (A of the n2f GEMM)
-            if (dalloc(sep_ey, (size_t)N * H)) return HGS_ERR_DEVICE;
-            if (dalloc(sep_nfT, (size_t)B * sep_Wk * sep_Hp)) return HGS_ERR_DEVICE;  // [B][Wk][Hp]
-            if (dalloc(sep_b2, (size_t)B * sep_Nk * sep_Hp)) return HGS_ERR_DEVICE;   // [B][Nk][Hp]
-            HIPCHK(sep_norm.alloc((size_t)B * ((N + 255) / 256)));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cgemm_streamk<0>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)CG_LDS_BYTES));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(cgemm_streamk<1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)CG_LDS_BYTES));
-        } else if (!sk_tab || !sep_c1 || !sep_c2) {      // (a change of HGS_OPT_SEP_WORKGROUPS that the device could not follow)
-            if (int e_ = sk_retable()) return e_;
-        }
-        HIPCHK(hipMemcpyAsync(sep_c, c.data(), c.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(sep_g, xs_host.data(), (size_t)W * sizeof(double), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(sep_g + W, ys_host.data(), (size_t)H * sizeof(double), hipMemcpyHostToDevice, stream));
-        sep_degx = dx;
-        sep_degy = dy;
-        hipLaunchKernelGGL(sep_build_table, dim3((W + 255) / 256, N), dim3(256), 0, stream, (const double*)sep_c, dx, N,
-                           (const double*)sep_g, W, sep_ex, sep_Wp, (size_t)sep_Nk * sep_Wp, sep_exT, sep_Np, (size_t)sep_Wk * sep_Np);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(sep_build_table, dim3((H + 255) / 256, N), dim3(256), 0, stream,
-                           (const double*)(sep_c + (size_t)(SEP_MAXDEG + 1) * N), dy, N, (const double*)(sep_g + W), H, sep_ey,
-                           H, (size_t)0, (float2*)nullptr, 0, (size_t)0);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));   // c / xs_host are host temporaries
-        c_sep = true;
-        return 0;
-    }
-    bool use_sep() const {
-        return c_sep && opt_separable && cfg.n_spots >= opt_sep_min;
-    }
-    // operands planar: real array at A / Bm, imaginary one planeA / planeB floats on.  E != nullptr: the epilogue contracts
-    // the result with E over its columns into `part` instead of storing it (n2f)
-    int launch_cgemm(const float* A, size_t planeA, const float* Bm, size_t planeB, float2* C, int M, int N, int KT, int lda, int ldb,
-                     int tiles_m, int tiles_n, int planes, const int* first_wg, int G, size_t strideA, size_t strideB,
-                     unsigned cap_flag, const float2* E = nullptr, int ldE = 0, float2* part = nullptr, int ldP = 0) {
-        CgemmSkArgs a{A, A + planeA, Bm, Bm + planeB, C, M, N, KT, lda, ldb, tiles_m, tiles_n, planes, first_wg, strideA, strideB,
-                      E, ldE, part, ldP};
-        if (E) { dispatch_note(dispatch_site<KCgemm, float, 1>(), bflag() | cap_flag); hipLaunchKernelGGL(cgemm_streamk<1>, dim3(G, B), dim3(256), CG_LDS_BYTES, stream, a); }
-        else { dispatch_note(dispatch_site<KCgemm, float, 0>(), bflag() | cap_flag); hipLaunchKernelGGL(cgemm_streamk<0>, dim3(G, B), dim3(256), CG_LDS_BYTES, stream, a); }
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    // n2f: T = Ex^T-table x nf^T on the matrix cores, contracted with Ey over y in the GEMM's epilogue
-    int sep_n2f() {
-        const int N = cfg.n_spots, H = g.Sh, W = g.Sw;
-        hipLaunchKernelGGL(sep_build_nft<R>, dim3((W + 31) / 32, (H + 31) / 32, B), dim3(32, 8), 0, stream, (const R*)phase,
-                           has_amp ? (const R*)amp : (const R*)nullptr, has_kern ? (const R*)kern : (const R*)nullptr,
-                           (R)amp_scalar, H, W, reinterpret_cast<float*>(sep_nfT.get()), sep_Hp, (size_t)sep_Wk * sep_Hp);
-        HIPCHK(hipGetLastError());
-        const int t1 = sk_tm1 * sk_tn1;
-        if (int e = launch_cgemm(reinterpret_cast<const float*>(sep_exT.get()), (size_t)sep_Wk * sep_Np,
-                                 reinterpret_cast<const float*>(sep_nfT.get()), (size_t)sep_Wk * sep_Hp, nullptr, N, H, sk_kt1, sep_Np, sep_Hp,
-                                 sk_tm1, sk_tn1, sep_split1, sk_tab, sk_G1, 0, (size_t)2 * sep_Wk * sep_Hp, sk_flag1,
-                                 (const float2*)sep_ey, H, sep_c1, sep_Np)) return e;
-        const int nred = (N + 255) / 256;
-        hipLaunchKernelGGL(sep_n2f_sum<R>, dim3(nred, B), dim3(256), 0, stream, (const float2*)sep_c1, sep_Np, sep_split1,
-                           (const int*)(sk_tab + t1), sk_tm1, sk_tn1, N, 1.0 / std::sqrt((double)S), ff, sep_norm);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(c_n2f_finish<R>, dim3(B), dim3(1024), 0, stream, cargs(), (const double*)sep_norm, nred);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    // f2n: conj(nf) = (conj(ff) Ey)^T x Ex on the matrix cores, then phase extraction (or the complex field)
-    int sep_f2n(Cx<R>* nf_out) {
-        const int N = cfg.n_spots, H = g.Sh, W = g.Sw;
-        hipLaunchKernelGGL(sep_build_b2<R>, dim3((H + 255) / 256, N, B), dim3(256), 0, stream, (const Cx<R>*)ff,
-                           (const float2*)sep_ey, N, H, reinterpret_cast<float*>(sep_b2.get()), sep_Hp, (size_t)sep_Nk * sep_Hp);
-        HIPCHK(hipGetLastError());
-        const int t1 = sk_tm1 * sk_tn1, t2 = sk_tm2 * sk_tn2;
-        if (int e = launch_cgemm(reinterpret_cast<const float*>(sep_b2.get()), (size_t)sep_Nk * sep_Hp,
-                                 reinterpret_cast<const float*>(sep_ex.get()), (size_t)sep_Nk * sep_Wp, sep_c2, H, W, sk_kt2, sep_Hp, sep_Wp,
-                                 sk_tm2, sk_tn2, sep_split2, sk_tab + 2 * t1, sk_G2, (size_t)2 * sep_Nk * sep_Hp, 0, sk_flag2)) return e;
-        hipLaunchKernelGGL(sep_f2n_finish<R>, dim3((unsigned)((S + 255) / 256), B), dim3(256), 0, stream, (const float2*)sep_c2,
-                           sep_split2, (const int*)(sk_tab + 2 * t1 + t2), sk_tm2, W, S,
-                           has_kern ? (const R*)kern : (const R*)nullptr, phase, nf_out);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-
-    CArgs<R> cargs() {
-        CArgs<R> a{};
-        a.S = (int)S; a.N = cfg.n_spots; a.M = cfg.n_monomials; a.batch = B; a.xg = xg; a.yg = yg; a.mono = mono;
-        a.coeff = coeff; a.phase = phase; a.amp = has_amp ? amp : nullptr; a.kern = has_kern ? kern : nullptr;
-        a.amp_scalar = (R)amp_scalar; a.ff = ff; a.amp_ff = aff; a.partial = cpartial; a.nblocks = c_nblocks;
-        a.fsum = sums + 0 * B; a.degree = c_degree;
-        return a;
-    }
     int compressed_ready() {
-        if (!has_grid[0] || !has_grid[1] || !has_mono || !has_coeff)
+        if (!comp.uploaded())
             return fail(HGS_ERR_STATE, "compressed engine needs HGS_XGRID, HGS_YGRID, HGS_MONOMIALS and HGS_SPOT_COEFF");
         return 0;
     }
@@ -976,23 +641,7 @@ template <typename R> struct Engine : EngineBase {
         if (int e = compressed_ready()) return e;
         if (int e = need_ff()) return e;
         if (store_pff) { if (int e = need_pff()) return e; }
-        const int nred = (int)((P + C_RED_SPOTS - 1) / C_RED_SPOTS);
-        int r = timed(HGS_K_COL_FWD, [&]() -> int {
-            if (use_sep()) return sep_n2f();
-            CArgs<R> a = cargs();
-            const dim3 grid(c_nblocks, B);
-            if (use_run()) { if (int e = run_n2f(a)) return e; }
-            else if (c_degree <= 1) { dispatch_note(dispatch_site<KCn2fPix, R, 1>(), bflag()); hipLaunchKernelGGL((c_n2f_partial<R, 1>), grid, dim3(C_WG), 0, stream, a); }
-            else if (c_degree == 2) { dispatch_note(dispatch_site<KCn2fPix, R, 2>(), bflag()); hipLaunchKernelGGL((c_n2f_partial<R, 2>), grid, dim3(C_WG), 0, stream, a); }
-            else if (cfg.n_monomials <= C_MTAB && tun.mono_tab) { dispatch_note(dispatch_site<KCn2fPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_n2f_partial<R, 3>), grid, dim3(C_WG), 0, stream, a); }
-            else { dispatch_note(dispatch_site<KCn2fPix, R, 0>(), bflag()); hipLaunchKernelGGL((c_n2f_partial<R, 0>), grid, dim3(C_WG), 0, stream, a); }
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(c_n2f_reduce<R>, dim3(nred, B), dim3(C_RED_SPOTS * C_RED_SLICES), 0, stream, a, cnorm);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(c_n2f_finish<R>, dim3(B), dim3(1024), 0, stream, a, (const double*)cnorm, nred);
-            HIPCHK(hipGetLastError());
-            return 0;
-        });
+        int r = timed(HGS_K_COL_FWD, [&]() -> int { return comp.n2f(cview()); });
         if (r) return r;
         if (store_pff) {
             EwArgs<R> a{};
@@ -1003,26 +652,10 @@ template <typename R> struct Engine : EngineBase {
         state.farfield_materialised(store_pff != 0);
         return 0;
     }
-    // the per-pixel compressed inverse, by polynomial degree (3: the monomial table; 0: any degree)
-    int pix_f2n(const CArgs<R>& a) {
-        const dim3 grid(c_nblocks, B);
-        if (c_degree <= 1) { dispatch_note(dispatch_site<KCf2nPix, R, 1>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 1>), grid, dim3(C_WG), 0, stream, a); }
-        else if (c_degree == 2) { dispatch_note(dispatch_site<KCf2nPix, R, 2>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 2>), grid, dim3(C_WG), 0, stream, a); }
-        else if (cfg.n_monomials <= C_MTAB && tun.mono_tab) { dispatch_note(dispatch_site<KCf2nPix, R, 3>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 3>), grid, dim3(C_WG), 0, stream, a); }
-        else { dispatch_note(dispatch_site<KCf2nPix, R, 0>(), bflag()); hipLaunchKernelGGL((c_f2n<R, 0>), grid, dim3(C_WG), 0, stream, a); }
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
     // nf_out: null extracts the phase; else the complex nearfield goes there and the phase stays (f2n_complex)
     int f2n_compressed(Cx<R>* nf_out = nullptr) {
         if (!ff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "no farfield to transform back");
-        int r = timed(HGS_K_COL_INV, [&]() -> int {
-            if (use_sep()) return sep_f2n(nf_out);
-            CArgs<R> a = cargs();
-            a.nf_out = nf_out;
-            if (use_run()) return run_f2n(a);
-            return pix_f2n(a);
-        });
+        int r = timed(HGS_K_COL_INV, [&]() -> int { return comp.f2n(cview(), nf_out); });
         state.farfield_consumed();
         return r;
     }
@@ -1195,49 +828,21 @@ template <typename R> struct Engine : EngineBase {
             case HGS_YGRID: {
                 if (cfg.kind != 1) return fail(HGS_ERR_STATE, "grids belong to the compressed engine");
                 if (nbytes != S * sizeof(R)) return fail(HGS_ERR_ARG, "grid: bad size %zu", nbytes);
-                if (int e_ = h2d(which == HGS_XGRID ? xg : yg, host, nbytes)) return e_;
-                has_grid[which == HGS_XGRID ? 0 : 1] = true;
                 state.geometry_changed();
-                {   // product grid?  x depends on the column only, y on the row only
-                    const R* h = (const R*)host;
-                    const int H = g.Sh, W = g.Sw;
-                    bool sep = true;
-                    if (which == HGS_XGRID) {
-                        for (int y = 1; y < H && sep; ++y)
-                            for (int x = 0; x < W; ++x)
-                                if (h[(size_t)y * W + x] != h[x]) { sep = false; break; }
-                        xs_host.assign(W, 0.0);
-                        for (int x = 0; x < W; ++x) xs_host[x] = (double)h[x];
-                    } else {
-                        for (int y = 0; y < H && sep; ++y)
-                            for (int x = 1; x < W; ++x)
-                                if (h[(size_t)y * W + x] != h[(size_t)y * W]) { sep = false; break; }
-                        ys_host.assign(H, 0.0);
-                        for (int y = 0; y < H; ++y) ys_host[y] = (double)h[(size_t)y * W];
-                    }
-                    grid_sep[which == HGS_XGRID ? 0 : 1] = sep;
-                }
-                return sep_refresh();
+                return comp.set_grid(cview(), which == HGS_XGRID ? 0 : 1, (const R*)host);
             }
             case HGS_MONOMIALS: {
                 if (cfg.kind != 1) return fail(HGS_ERR_STATE, "monomials belong to the compressed engine");
                 if (nbytes != (size_t)2 * cfg.n_monomials * sizeof(int32_t)) return fail(HGS_ERR_ARG, "monomials: bad size");
-                const int32_t* h = (const int32_t*)host;
-                if (has_mono && std::equal(mono_host.begin(), mono_host.end(), h)) return 0;   // unchanged term set
-                mono_host.assign(h, h + 2 * cfg.n_monomials);
-                if (int e_ = h2d(mono, host, nbytes)) return e_;
-                has_mono = true;
+                if (comp.same_monomials((const int32_t*)host)) return 0;   // unchanged term set
                 state.geometry_changed();
-                return pack_coeff();
+                return comp.set_monomials(cview(), (const int32_t*)host);
             }
             case HGS_SPOT_COEFF: {
                 if (cfg.kind != 1) return fail(HGS_ERR_STATE, "spot coefficients belong to the compressed engine");
                 if (nbytes != (size_t)cfg.n_monomials * cfg.n_spots * sizeof(R)) return fail(HGS_ERR_ARG, "spot coefficients: bad size");
-                const R* h = (const R*)host;
-                coeff_host.assign(h, h + (size_t)cfg.n_monomials * cfg.n_spots);
-                has_coeff = true;
                 state.geometry_changed();
-                return pack_coeff();
+                return comp.set_coeff(cview(), (const R*)host);
             }
             case HGS_SPOT_INDEX: {
                 if (cfg.n_spots <= 0) return fail(HGS_ERR_STATE, "engine was created with n_spots = 0");
@@ -2436,17 +2041,12 @@ template <typename R> struct Engine : EngineBase {
             case HGS_OPT_SPARSE_COLUMNS: tun.sparse = value ? 1 : 0; return 0;
             case HGS_OPT_FORCE_STEPWISE: opt_stepwise = value ? 1 : 0; return 0;
             case HGS_OPT_TILE_KERNEL: tun.tile = value ? 1 : 0; state.scan_policy_changed(); return 0;
-            case HGS_OPT_SEPARABLE: opt_separable = value ? 1 : 0; return 0;
-            case HGS_OPT_SEPARABLE_MIN_SPOTS: opt_sep_min = value > 0 ? value : 1; return 0;
+            case HGS_OPT_SEPARABLE: comp.opt_separable = value ? 1 : 0; return 0;
+            case HGS_OPT_SEPARABLE_MIN_SPOTS: comp.opt_sep_min = value > 0 ? value : 1; return 0;
             case HGS_OPT_SEP_WORKGROUPS:
                 if (value < 0) return fail(HGS_ERR_ARG, "HGS_OPT_SEP_WORKGROUPS must be 0 (2 x #CU) or a positive workgroup count, got %d", value);
-                if (value == opt_sep_wg) return 0;
-                opt_sep_wg = value;
-                // the tables exist already: rebuild them and the plane buffers they size
-                if (sep_c)
-                    if (int e_ = sk_retable()) { c_sep = false; return e_; }
-                return 0;
-            case HGS_OPT_RUN_KERNELS: opt_run = value ? 1 : 0; return 0;
+                return comp.set_sep_workgroups(cview(), value);
+            case HGS_OPT_RUN_KERNELS: comp.opt_run = value ? 1 : 0; return 0;
             case HGS_OPT_EMPTY_COL_LOADS: tun.empty_col_loads = value ? 1 : 0; return 0;
             case HGS_OPT_KEEP_PREV_PHASE: opt_prev_phase = value ? 1 : 0; if (!value) state.prev_phase_dropped(); return 0;
             case HGS_OPT_ROCTX:

@@ -7,10 +7,13 @@
 
 namespace hgs {
 
-// kernel family tag (dispatch.hpp) -> kernel template
+// kernel family tag (dispatch.hpp) -> kernel template.  HGS_BIND_F32: a kernel without an element-type parameter (fp32
+// only); its instances are launched and recorded with R = float.  (compressed_backend.hpp binds its kernels with the same two.)
 template <typename Fam> struct KernelOf;
 #define HGS_BIND(tag, kernel) \
     template <> struct KernelOf<tag> { template <typename R, auto... V> static auto ptr() { return kernel<R, V...>; } }
+#define HGS_BIND_F32(tag, kernel) \
+    template <> struct KernelOf<tag> { template <typename R, auto... V> static auto ptr() { return kernel<V...>; } }
 HGS_BIND(KRow, row_kernel);
 HGS_BIND(KCol, col_kernel);
 HGS_BIND(KFused, col_fused_kernel);
@@ -18,23 +21,27 @@ HGS_BIND(KTile, col_tile_kernel);
 HGS_BIND(KTile2, col_tile2_kernel);
 HGS_BIND(KPresum, col_presum_kernel);
 HGS_BIND(KBlue, bluestein_lines);
-#undef HGS_BIND
 
 // Launches instance <R, V...> of family Fam and notes exactly that instance in the dispatch record: the kernel and the
 // recorded site come from the same argument pack, so the record cannot name another instance than the one that ran.  V
 // names EVERY template argument of the kernel after R (also those it has defaults for): DispatchLog::text() pairs the
-// values with the family's parameter names.  `lds`: dynamic LDS in bytes; above 48 KB the kernel is allowed that much
-// first.  Returns hipError_t as int.
+// values with the family's parameter names.  `lds`: dynamic LDS in bytes; launch_instance allows the kernel more than
+// 48 KB of it first, launch_noted leaves that to a caller who did so once, when it made the kernel's tables.  Both
+// return hipError_t as int.
+template <typename Fam, typename R, auto... V, typename... Args>
+static inline int launch_noted(dim3 grid, dim3 block, size_t lds, hipStream_t s, unsigned flags, const Args&... args) {
+    dispatch_note(dispatch_site<Fam, R, V...>(), flags);
+    hipLaunchKernelGGL((KernelOf<Fam>::template ptr<R, V...>()), grid, block, lds, s, args...);
+    return (int)hipGetLastError();
+}
 template <typename Fam, typename R, auto... V, typename... Args>
 static inline int launch_instance(dim3 grid, dim3 block, size_t lds, hipStream_t s, unsigned flags, const Args&... args) {
-    auto k = KernelOf<Fam>::template ptr<R, V...>();
     if (lds > 48 * 1024) {
+        auto k = KernelOf<Fam>::template ptr<R, V...>();
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    dispatch_note(dispatch_site<Fam, R, V...>(), flags);
-    hipLaunchKernelGGL(k, grid, block, lds, s, args...);
-    return (int)hipGetLastError();
+    return launch_noted<Fam, R, V...>(grid, block, lds, s, flags, args...);
 }
 
 template <typename R> inline unsigned row_flags(dim3 grid, const RowArgs<R>& a) {

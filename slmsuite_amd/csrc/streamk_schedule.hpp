@@ -1,6 +1,6 @@
 // The stream-K schedule of cgemm_streamk (cgemm.hpp), as plain functions: which steps a workgroup walks, which workgroup
 // owns a step, and per output tile the first workgroup and the number of partial planes its k-steps are spread over.
-// Plain C++ -- no HIP, no engine state, no device -- so that the kernel, the engine's tables (Engine::sep_refresh_impl) and
+// Plain C++ -- no HIP, no engine state, no device -- so that the kernel, the engine's tables (CompressedBackend::sk_retable) and
 // the microbenchmark share one statement of it and the schedule can be swept without a GPU
 // (tests/test_streamk_schedule.py replays the kernel's control flow against these tables).
 //
