@@ -18,6 +18,7 @@ OPT_RUN_KERNELS = 7
 OPT_KEEP_PREV_PHASE = 8
 OPT_EMPTY_COL_LOADS = 9
 OPT_SEP_WORKGROUPS = 10
+OPT_EMPTY_COL_INVERSE = 11
 
 # array selectors (include/hgs.h)
 (PHASE, AMP, AMP_SCALAR, PROP_KERNEL, TARGET, WEIGHTS, PHASE_FF, FARFIELD, AMP_FF, SPOT_INDEX,

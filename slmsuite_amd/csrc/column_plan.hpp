@@ -40,6 +40,8 @@ struct Tuning {
     int presum_blocks = 0;      // HGS_PRESUM_BLOCKS: workgroups of the pre-pass (0 = tuned)
     int empty_col_loads = 1;    // HGS_EMPTY_COL_LOADS=0 / HGS_OPT_EMPTY_COL_LOADS: the half-width tile kernel fetches weights and targets of
                                 // every column, also of those the scan found empty (the tests' A/B reference)
+    int empty_col_inverse = 1;  // HGS_EMPTY_COL_INVERSE=0 / HGS_OPT_EMPTY_COL_INVERSE: ... and runs the rule block and the inverse transform
+                                // of those columns as well (the flags still go with the launch)
     int sparse = 1;             // HGS_OPT_SPARSE_COLUMNS
     int tile = 1;               // HGS_OPT_TILE_KERNEL (0 forces the per-column kernel at every size: the tests' A/B reference)
 };

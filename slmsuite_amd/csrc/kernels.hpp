@@ -1054,6 +1054,8 @@ template <typename R> struct ColArgs {
     int n_dpartial;           // of D = sum w'^2 - sum w^2 over the signal pixels, left by col_presum_kernel (written there through
                               // wpartial's neighbour, see engine.hip); 1 / ||w'|| = 1 / sqrt(1 + D) is known BEFORE the field is rebuilt
     int few_active;        // at most a quarter of the farfield columns hold a non-zero weight or target (col_tile2_kernel NXF)
+    int zero_inv;          // col_tile2_kernel with col_flags (HGS_OPT_EMPTY_COL_INVERSE): a column whose bit 0 is clear skips the rule
+                           // block and its inverse transform -- the constrained column is exactly zero, so is its inverse
     int fnr;               // col_fused_kernel: register slots the shifted SLM rows occupy (0 = the unshifted kernel, NRS = 16)
     int fshift;            // col_fused_kernel<..., NRS < 16> (float64, >= 4096 rows): circular shift of the transform input, a
                            // multiple of 16 rows (shift theorem, as in col_tile_kernel): the SLM rows occupy slots 0 .. NRS - 1
@@ -2501,6 +2503,18 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
             const float4* pq = PFQ ? reinterpret_cast<const float4*>(pfc + lane_pos<T>(j, 0)) : nullptr;
             float4 qa = make_float4(0, 0, 0, 0), qb = qa;
             if constexpr (PFQ) { qa = pq[0]; qb = pq[1]; }
+            // An EMPTY column (bit 0 of its scan byte clear, a.zero_inv): weight and target are zero in every pixel, every pixel
+            // below would take the wave_all_zero exit and the inverse would transform sixteen zeros per lane.  Both are
+            // skipped; slots 0 .. NR-1 become +0 and the code after the inverse writes them where it writes every column's H.  The
+            // condition is a scalar of the flag word, the same in all four waves: every wave skips the same barriers.
+            // LDS (comment above WgFftL): the forward transform above ended with a barrier and writes only the writing wave's
+            // own regions, so the next forward transform may follow it directly, as in col_presum_kernel.
+            // The requests for the next column and the weight stores stay outside the branch: both paths reach the head of
+            // the column loop with the same requests in flight.
+            bool empty_col = false;
+            if constexpr (WTBUF && PHASE == 0)
+                empty_col = cflag4 != nullptr && a.zero_inv != 0 && ((fw >> (16 * half + 8 * c)) & 1) == 0;
+            if (!empty_col)
             static_for<0, 16>([&](auto m_) {
                 constexpr int m = m_;
                 if constexpr (PFQ && m == 4) qa = pq[2];            // (pixels 0-3 are through)
@@ -2558,7 +2572,12 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 }
             }
             HGS_T(fft.tr_n, 5);
-            fft.template inv_after_fwd_trail<NR>(v, lds, j);
+            if (!empty_col) {
+                fft.template inv_after_fwd_trail<NR>(v, lds, j);
+            } else {
+#pragma unroll
+                for (int m = 0; m < NR; ++m) v[m] = mk<R>(0, 0);
+            }
             HGS_T(fft.tr_n, 6);
             if constexpr (PARK) {
                 if (c == 0) {
