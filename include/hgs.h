@@ -122,8 +122,10 @@ enum {
                              STARTED from (HGS_OPT_KEEP_PREV_PHASE); HGS_ERR_STATE when none is held */
     HGS_CG_GRAD = 18,     /* get only: [slm_h][slm_w] real -- dL/dphase of the last hgs_cg_iterate body that kept it
                              (hgs_cg_params.keep_grad); HGS_ERR_STATE before the first such body */
-    HGS_VORTICES = 19     /* get only: int32 [n][3] (x, y, winding) -- the vortices the last hgs_remove_vortices call found and
+    HGS_VORTICES = 19,    /* get only: int32 [n][3] (x, y, winding) -- the vortices the last hgs_remove_vortices call found and
                              removed, n its n_removed; HGS_ERR_STATE before the first call */
+    HGS_DISPLAY_CORRECTION = 20 /* hgs_set_array only: DOUBLE [slm_h][slm_w] in either precision -- the wavefront correction
+                             hgs_get_display adds (slm.source["phase"], float64 in the reference); nbytes = 0: none */
 };
 
 int hgs_create(const hgs_config* cfg, hgs_engine** out);
@@ -220,6 +222,32 @@ int hgs_cg_iterate(hgs_engine* e, const hgs_cg_params* params, int n_iter, doubl
  * farfield, amp_ff, the weights, the phase and the statistics are untouched.  kind 0 and batch 1 only (HGS_ERR_UNSUPPORTED
  * otherwise); HGS_ERR_STATE when no phase_ff is held or no target is set; power-of-two and general padded shapes alike. */
 int hgs_remove_vortices(hgs_engine* e, int32_t* n_removed);
+
+/* The gray levels an SLM takes, from the device phase: Hologram.get_phase (_hologram.py:786-811), the float branch of
+ * SLM.set_phase (hardware/slms/slm.py:664-681) and SLM._phase2gray (:695-783), equal to the reference bit for bit.
+ * With R = 2^bitdepth and s = phase_scaling, per pixel
+ *     p = phase + pi in the engine's precision (pi rounded to it) -- with include_propagation and a kernel held:
+ *         phase + kernel, no pi; without a kernel the flag changes nothing, as in the reference;
+ *     x = p widened to double, plus HGS_DISPLAY_CORRECTION where one is held and phase_correct != 0;
+ *     y = x * f,  f = -(R * s / 2 / pi);
+ *     s == 1:  m = max y over the hologram;  m >= 0: y -= R * 2 * ceil(m / R);  out = (rint(y) - 1) & (R - 1);
+ *     s != 1:  min y <= -R or max y > 0:  y -= 1,  y = mod(y, R s) with the divisor's sign,  y += R (1 - s),  and for s > 1
+ *              y < 0 -> R - 1;  otherwise y += R - 1;  out = y truncated toward zero.
+ * Every product and sum rounds on its own (no fused multiply-add): the shift of the s == 1 branch depends on the data and
+ * moves values onto rounding ties.  The extremes are those of ONE hologram -- the reference converts one mask per call --
+ * and never leave the device: a range pass and a convert pass, no host synchronisation in between.  NaN phases are
+ * undefined, as in the reference.  Output: [batch][slm_h][slm_w] of uint8 (bitdepth <= 8) or uint16, nbytes exactly that;
+ * both engine kinds, any batch.  The phase, the farfield and every other array are untouched. */
+typedef struct {
+    double  phase_scaling;       /* wav_um / wav_design_um, > 0 */
+    int32_t bitdepth;            /* 1..16 */
+    int32_t include_propagation;
+    int32_t phase_correct;
+    int32_t reserved;
+} hgs_display_params;
+int hgs_get_display(hgs_engine* e, const hgs_display_params* p, void* host, size_t nbytes);
+/* ... into a caller-provided DEVICE buffer (e.g. a torch tensor); synchronous */
+int hgs_get_display_device(hgs_engine* e, const hgs_display_params* p, void* dev, size_t nbytes);
 
 /* MultiplaneHologram._farfield2nearfield (_multiplane.py:255-279): every child runs
  * _farfield2nearfield(extract=False) on its own (constrained) farfield; the children's complex
@@ -322,7 +350,7 @@ int hgs_iterate_timed(hgs_engine* e, hgs_step* step, int n_iter, double* ms);
  * (family, its template arguments by name -- the ones rocprofv3 prints positionally --, flags list / load_mask /
  * store_mask / xmap / batch / stats / nf_out, launch count).  Families: row_kernel, col_kernel, col_fused_kernel,
  * col_tile_kernel, bluestein_lines, c_n2f_run, c_f2n_run, c_n2f_partial, c_f2n, cgemm_streamk, cg_seed_kernel, cg_adam_kernel,
- * vortex_find_kernel, vortex_remove_kernel
+ * vortex_find_kernel, vortex_remove_kernel, phase_display_kernel
  * (the small element-wise / reduction helpers are not recorded).  The tests assert it next to the numbers: neighbouring variants often agree to
  * the last bit, so only this shows that a policy reached the kernel it names.  `needed` (optional) receives the bytes
  * the text takes including the terminator; with buf = NULL and nbytes = 0 the call is a size query and keeps the record,

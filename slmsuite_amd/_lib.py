@@ -26,6 +26,7 @@ OPT_EMPTY_COL_INVERSE = 11
 PHASE_PREV = 17
 CG_GRAD = 18
 VORTICES = 19
+DISPLAY_CORRECTION = 20
 FB_PIXEL, FB_SPOT_WINDOW, FB_EXTERNAL = 0, 1, 2
 K_NAMES = ("row", "col_fused", "col_fwd", "col_inv", "elementwise", "cg_seed", "cg_adam")
 
@@ -45,6 +46,11 @@ class hgs_step(C.Structure):
 
 class hgs_cg_params(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps")] + [(n, C.c_int32) for n in ("restart", "keep_grad")]
+
+
+class hgs_display_params(C.Structure):
+    _fields_ = [("phase_scaling", C.c_double)] + \
+               [(n, C.c_int32) for n in ("bitdepth", "include_propagation", "phase_correct", "reserved")]
 
 
 _lib = None
@@ -114,6 +120,8 @@ def load():
                                         P(C.c_double), P(C.c_double)]),
         "hgs_cg_iterate": (C.c_int, [eng, P(hgs_cg_params), C.c_int, P(C.c_double)]),
         "hgs_remove_vortices": (C.c_int, [eng, P(C.c_int32)]),
+        "hgs_get_display": (C.c_int, [eng, P(hgs_display_params), C.c_void_p, C.c_size_t]),
+        "hgs_get_display_device": (C.c_int, [eng, P(hgs_display_params), C.c_void_p, C.c_size_t]),
         "hgs_sync": (C.c_int, [eng]),
         "hgs_set_option": (C.c_int, [eng, C.c_int, C.c_int]),
         "hgs_profile_enable": (C.c_int, [eng, C.c_int]),
@@ -133,7 +141,7 @@ def load():
 
 EXPORTS = ("hgs_create", "hgs_destroy", "hgs_set_array", "hgs_get_array", "hgs_get_array_device", "hgs_set_array_device", "hgs_copy_phase",
            "hgs_reset_weights", "hgs_reset", "hgs_set_array_sparse", "hgs_nearfield2farfield", "hgs_farfield_constraint",
-           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_cg_iterate", "hgs_remove_vortices", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
+           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_cg_iterate", "hgs_remove_vortices", "hgs_get_display", "hgs_get_display_device", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
            "hgs_profile_read", "hgs_iterate_timed", "hgs_dispatch_read", "hgs_last_error", "hgs_version")
 
 

@@ -11,7 +11,7 @@ import numpy as np
 
 from slmsuite_amd import _lib as L
 from slmsuite_amd.engine import Engine, make_step
-from slmsuite_amd.holography.algorithms import ALGORITHM_DEFAULTS
+from slmsuite_amd.holography.algorithms import ALGORITHM_DEFAULTS, _fingerprint
 
 
 def batch_flags(method, **flags):
@@ -216,6 +216,17 @@ class HologramBatch:
 
     def phases(self):
         return np.concatenate([e.get(L.PHASE) for e in self.engines], axis=0)
+
+    def displays(self, bitdepth=8, phase_scaling=1.0, phase_correction=None, include_propagation=False):
+        """``[n, Sh, Sw]`` gray levels of every hologram's phase (``Engine.get_display``: uint8 for ``bitdepth <= 8``, else
+        uint16), each converted with its own extremes as ``SLM.set_phase`` would one mask at a time; ``phase_correction``
+        (float64 ``slm_shape`` or None) is added to every one.  It goes to an engine only when it changed since that engine
+        was last sent one (``algorithms._fingerprint``, as ``Hologram.get_display``) and stays there for the next call."""
+        fp = _fingerprint(phase_correction)
+        for e in self.engines:
+            e.send_display_correction(phase_correction, fp)
+        return np.concatenate([e.get_display(bitdepth=bitdepth, phase_scaling=phase_scaling,
+                                             include_propagation=include_propagation) for e in self.engines], axis=0)
 
     def phases_into_device(self, dev_ptr, nbytes):
         """Copy the [n, Sh, Sw] phase masks into caller-owned DEVICE memory (e.g. a torch tensor handed to RCCL)."""

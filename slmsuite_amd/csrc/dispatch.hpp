@@ -72,6 +72,7 @@ HGS_FAMILY(KCgSeed, "cg_seed_kernel", "R");
 HGS_FAMILY(KCgAdam, "cg_adam_kernel", "R");
 HGS_FAMILY(KVortexFind, "vortex_find_kernel", "R");
 HGS_FAMILY(KVortexRemove, "vortex_remove_kernel", "R");
+HGS_FAMILY(KDisplay, "phase_display_kernel", "R,BITS");
 #undef HGS_FAMILY
 
 }  // namespace hgs

@@ -21,6 +21,7 @@
 #include "bluestein.hpp"
 #include "cg_kernels.hpp"
 #include "vortex_kernels.hpp"
+#include "display_kernels.hpp"
 #include <complex>
 #include <dlfcn.h>
 
@@ -161,6 +162,7 @@ struct EngineBase {
     virtual int iterate_timed(hgs_step* st, int n, double* ms) = 0;
     virtual int cg_iterate(const hgs_cg_params* p, int n, double* loss_out) = 0;
     virtual int remove_vortices(int32_t* n_removed) = 0;
+    virtual int get_display(const hgs_display_params* p, void* dst, size_t nbytes, bool dst_device) = 0;
 };
 
 template <typename R> struct Engine : EngineBase {
@@ -216,6 +218,11 @@ template <typename R> struct Engine : EngineBase {
     DevBuf<int32_t> vx_list, vx_count;
     unsigned vx_cap = 0;
     int vx_n = -1;
+    // hgs_get_display: the wavefront correction (HGS_DISPLAY_CORRECTION, double in either precision), the (max, min) pairs of
+    // the range pass and the gray levels before they leave (the kernels store packed quads: an address of the engine's own)
+    DevBuf<double> disp_corr, disp_partial;
+    DevBuf<char> disp_out;
+    bool has_disp_corr = false;
     // per-column kernel (float64; float32 where the tile-resident kernel does not run) single-pass MRAF: noise part as farfield
     // values, the columns that hold it, their inverse pass
     DevBuf<C> ffb;                      // [B][P], layout of ff; only NaN-target pixels are ever written, the rest stays zero
@@ -750,6 +757,17 @@ template <typename R> struct Engine : EngineBase {
         if (which == HGS_PROP_KERNEL && nbytes == 0) {       // "no kernel" (Hologram.propagation_kernel = None / 0)
             has_kern = false;
             state.nearfield_input_changed();
+            return 0;
+        }
+        if (which == HGS_DISPLAY_CORRECTION) {               // not a nearfield input: the loop never sees it
+            if (src_device) return fail(HGS_ERR_UNSUPPORTED, "the display correction is uploaded with hgs_set_array");
+            if (nbytes == 0) { has_disp_corr = false; return 0; }
+            if (!host) return fail(HGS_ERR_ARG, "null source pointer");
+            if (nbytes != S * sizeof(double)) return fail(HGS_ERR_ARG, "display correction: bad size %zu (%zu doubles expected)", nbytes, S);
+            HIPCHK(disp_corr.ensure(S));
+            has_disp_corr = false;
+            if (int e_ = h2d(disp_corr, host, nbytes)) return e_;
+            has_disp_corr = true;
             return 0;
         }
         if (!host) return fail(HGS_ERR_ARG, "null source pointer");
@@ -1332,6 +1350,40 @@ template <typename R> struct Engine : EngineBase {
         vx_n = n;
         if (n_removed) *n_removed = n;
         return 0;
+    }
+
+    // SLM.set_phase(hologram) up to the hardware write, on the device (include/hgs.h, display_kernels.hpp): the range pass
+    // leaves the extremes of the scaled phase per hologram, the convert pass applies the branch they select.  Reads the
+    // phase, the kernel and the correction; writes nothing the loop knows of.
+    int get_display(const hgs_display_params* p, void* dst, size_t nbytes, bool dst_device) override {
+        RoctxRange range(opt_roctx, "hgs_get_display");
+        if (!dst) return fail(HGS_ERR_ARG, "null destination pointer");
+        if (p->bitdepth < 1 || p->bitdepth > 16) return fail(HGS_ERR_ARG, "hgs_get_display: bitdepth must be in 1..16 (got %d)", p->bitdepth);
+        if (!(p->phase_scaling > 0) || !std::isfinite(p->phase_scaling))
+            return fail(HGS_ERR_ARG, "hgs_get_display: phase_scaling must be positive and finite (got %g)", p->phase_scaling);
+        const bool bits16 = p->bitdepth > 8;
+        const size_t all = (size_t)B * S * (bits16 ? 2 : 1);
+        if (nbytes != all) return fail(HGS_ERR_ARG, "hgs_get_display: bad size %zu (%zu expected: %d-bit levels)", nbytes, all, bits16 ? 16 : 8);
+        DisplayArgs<R> a{};
+        a.range_blocks = display_range_blocks(S);
+        if (need(disp_partial, (size_t)2 * B * a.range_blocks)) return HGS_ERR_DEVICE;
+        if (need(disp_out, (size_t)B * S * 2)) return HGS_ERR_DEVICE;      // (made once: room for 16-bit levels whatever this call asks for)
+        // the reference's own expressions, in its order of evaluation, in double
+        const double res = (double)(1 << p->bitdepth), s = p->phase_scaling;
+        a.phase = phase;
+        a.kern = p->include_propagation && has_kern ? kern.get() : nullptr;
+        a.corr = p->phase_correct && has_disp_corr ? disp_corr.get() : nullptr;
+        a.partial = disp_partial; a.out = disp_out.get(); a.S = S;
+        a.unit = s == 1.0; a.fill = s > 1.0;
+        a.f = a.unit ? -(res / 2 / M_PI) : -(res * s / 2 / M_PI);
+        a.res = res; a.period = res * s; a.lift = res * (1 - s);
+        int r = timed(HGS_K_ELEMENTWISE, [&]() -> int {
+            LCHK(launch_display_range<R>(B, stream, a));
+            LCHK(launch_display<R>(B, bits16, stream, a));
+            return 0;
+        });
+        if (r) return r;
+        return d2h(dst, disp_out, all, dst_device);
     }
 
     int mp_info(MpInfo* o) override {
@@ -2185,6 +2237,16 @@ int hgs_cg_iterate(hgs_engine* e, const hgs_cg_params* params, int n_iter, doubl
     return e->impl->cg_iterate(params, n_iter, loss_out);
 }
 int hgs_remove_vortices(hgs_engine* e, int32_t* n_removed) { ENG(e) return e->impl->remove_vortices(n_removed); }
+int hgs_get_display(hgs_engine* e, const hgs_display_params* p, void* host, size_t nbytes) {
+    ENG(e)
+    if (!p) return hgs::fail(HGS_ERR_ARG, "null parameters");
+    return e->impl->get_display(p, host, nbytes, false);
+}
+int hgs_get_display_device(hgs_engine* e, const hgs_display_params* p, void* dev, size_t nbytes) {
+    ENG(e)
+    if (!p) return hgs::fail(HGS_ERR_ARG, "null parameters");
+    return e->impl->get_display(p, dev, nbytes, true);
+}
 int hgs_iterate_stats(hgs_engine* e, hgs_step* step, int n_iter, uint8_t* hist, int stat_groups, int width,
                       const double* spot_xy_float, double* stats_out) {
     ENG(e)

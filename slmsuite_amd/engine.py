@@ -226,6 +226,53 @@ class Engine:
         L.check(self.lib.hgs_get_array(self._h, L.VORTICES, out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
 
+    def set_display_correction(self, arr):
+        """HGS_DISPLAY_CORRECTION: the wavefront correction ``get_display`` adds (``slm.source["phase"]``), ``slm_shape``,
+        held as float64 whatever the engine's precision; ``None`` clears it."""
+        self._display_fp = self._NOT_SENT
+        if arr is None:
+            L.check(self.lib.hgs_set_array(self._h, L.DISPLAY_CORRECTION, None, 0))
+            return
+        a = np.ascontiguousarray(arr, dtype=np.float64)
+        if a.shape != self.slm_shape:
+            raise ValueError(f"display correction of shape {a.shape} is not of slm_shape {self.slm_shape}")
+        L.check(self.lib.hgs_set_array(self._h, L.DISPLAY_CORRECTION, a.ctypes.data_as(C.c_void_p), a.nbytes))
+
+    _NOT_SENT = object()
+
+    def send_display_correction(self, arr, fingerprint):
+        """``set_display_correction(arr)`` unless ``fingerprint`` equals that of the last array sent this way.  The record
+        lives with the engine: a new engine holds no correction and is sent one whatever an earlier engine was sent."""
+        if self.__dict__.get("_display_fp", self._NOT_SENT) != fingerprint:
+            self._display_fp = self._NOT_SENT              # (a refused upload leaves nothing on record)
+            self.set_display_correction(arr)
+            self._display_fp = fingerprint
+
+    def forget_display_correction(self):
+        """The next ``send_display_correction`` uploads whatever it is handed."""
+        self._display_fp = self._NOT_SENT
+
+    def get_display(self, bitdepth=8, phase_scaling=1.0, include_propagation=False, phase_correct=True, get=True):
+        """
+        hgs_get_display: the gray levels of the current phase as ``SLM.set_phase(hologram)`` of the reference forms them
+        (``get_phase()``, the wavefront correction, ``_phase2gray``), bit for bit, ``[batch, h, w]`` of uint8
+        (``bitdepth <= 8``) or uint16.  ``get=False``: a torch tensor on the engine's GPU, no host copy.
+        """
+        prm = L.hgs_display_params(phase_scaling=float(phase_scaling), bitdepth=int(bitdepth),
+                                   include_propagation=int(bool(include_propagation)),
+                                   phase_correct=int(bool(phase_correct)), reserved=0)
+        wide = int(bitdepth) > 8
+        shape = (self.batch,) + self.slm_shape
+        if get:
+            out = np.empty(shape, dtype=np.uint16 if wide else np.uint8)
+            L.check(self.lib.hgs_get_display(self._h, C.byref(prm), out.ctypes.data_as(C.c_void_p), out.nbytes))
+            return out
+        import torch
+        t = torch.empty(shape, dtype=torch.uint16 if wide else torch.uint8, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(t.device).synchronize()     # (the block may be a recycled one torch is still reading)
+        L.check(self.lib.hgs_get_display_device(self._h, C.byref(prm), C.c_void_p(t.data_ptr()), t.numel() * t.element_size()))
+        return t
+
     def iterate_timed(self, step, n_iter):
         ms = C.c_double()
         L.check(self.lib.hgs_iterate_timed(self._h, C.byref(step), int(n_iter), C.byref(ms)))

@@ -152,3 +152,116 @@ class SimpleFourierSLM:
         if hasattr(self.slm, "set_phase"):
             self.slm.set_phase(hologram.get_phase(), settle=True)
         return hologram
+
+
+def phase_to_gray(mask, bitdepth, phase_scaling):
+    """
+    The gray levels of a float64 mask in radians (``SLM._phase2gray``, slm.py:695-783), on the host.  Returns
+    ``(display, phase)``: the levels (uint8 for ``bitdepth <= 8``, else uint16) and the mask as the reference leaves it
+    behind -- it scales in place and scales back, so ``slm.phase`` afterwards is the quantised (``phase_scaling == 1``) or
+    wrapped mask, not the input.  ``hgs_get_display`` is the device form of the same arithmetic (include/hgs.h).
+    """
+    levels = 2 ** int(bitdepth)
+    unit = phase_scaling == 1
+    factor = -(levels / 2 / np.pi) if unit else -(levels * phase_scaling / 2 / np.pi)
+    y = np.array(mask, dtype=np.float64) * factor
+    if unit:
+        top = np.amax(y)
+        if top >= 0:                                  # all negative before rounding: the shift depends on the data
+            y -= levels * 2 * float(np.ceil(top / levels))
+        np.rint(y, out=y)
+        display = (y.astype(np.int64) - 1) & (levels - 1)
+    else:
+        if np.amin(y) <= -levels or np.amax(y) > 0:
+            y -= 1
+            np.mod(y, levels * phase_scaling, out=y)
+            y += levels * (1 - phase_scaling)
+            if phase_scaling > 1:
+                y[y < 0] = levels - 1
+        else:
+            y += levels - 1
+        display = y.astype(np.int64)                  # truncation toward zero
+    y *= 1 / factor
+    return display.astype(np.uint8 if bitdepth <= 8 else np.uint16), y
+
+
+class DisplaySLM(SimpleSLM):
+    """
+    A :class:`SimpleSLM` that also forms what the panel is sent: ``bitdepth``, ``wav_design_um`` -> ``phase_scaling``,
+    ``phase_correct``, ``phase`` and ``display`` as the reference's ``SLM`` keeps them (slm.py:136-230), and
+    ``set_phase`` (slm.py:472-693) without the hardware write and the settle delay.  A hologram is converted on the GPU
+    (``hologram.get_display(self)``), arrays on the host.  ``source["phase"]``, when present, is the wavefront correction.
+    """
+
+    def __init__(self, shape, pitch_um=(8.0, 8.0), wav_um=0.78, source_radius=None, bitdepth=8, wav_design_um=None):
+        super().__init__(shape, pitch_um=pitch_um, wav_um=wav_um, source_radius=source_radius)
+        self.bitdepth = int(bitdepth)
+        if not 1 <= self.bitdepth <= 16:
+            raise ValueError(f"bitdepth must be in 1..16 (got {bitdepth})")
+        self.wav_design_um = self.wav_um if wav_design_um is None else float(wav_design_um)
+        self.phase_scaling = self.wav_um / self.wav_design_um
+        self.dtype = np.dtype(np.uint8 if self.bitdepth <= 8 else np.uint16)
+        self.phase_correct = True
+        self._phase = np.zeros(self.shape)
+        self._phase_from = None        # (hologram, phase_correct) of a device conversion not yet mirrored in phase
+        self.display = np.zeros(self.shape, dtype=self.dtype)
+
+    @property
+    def bitresolution(self):
+        return 2 ** self.bitdepth
+
+    @property
+    def phase(self):
+        """The float64 mask behind ``display``.  After ``set_phase(hologram)`` it is built on first read -- the device
+        conversion downloads no phase --: ``hologram.get_phase()`` plus the correction, then what the host conversion of that
+        array leaves behind (the reference scales ``phase`` in place and back).  That read uses the hologram's phase AT THE
+        TIME OF THE READ: if the hologram was optimised or assigned a phase between ``set_phase`` and the first read, ``phase``
+        no longer describes ``display``; read it before touching the hologram where the pair matters."""
+        if self._phase_from is not None:
+            hologram, correct = self._phase_from
+            self._phase_from = None
+            _, self._phase = phase_to_gray(self._mask(hologram.get_phase(), correct), self.bitdepth, self.phase_scaling)
+        return self._phase
+
+    @phase.setter
+    def phase(self, value):
+        self._phase_from = None
+        self._phase = value
+
+    def _mask(self, phase, correct):
+        """float64 copy of a float array, unpadded to the SLM's shape, plus the correction where requested (slm.py:664-677)."""
+        mask = np.array(phase, dtype=np.float64)
+        if mask.shape != self.shape:
+            mask = np.array(_unpad(mask, self.shape))
+        if correct and "phase" in self.source:
+            mask += np.asarray(self.source["phase"])
+        return mask
+
+    def set_phase(self, phase, phase_correct=None, settle=None):
+        """``SLM.set_phase`` for a hologram, a float array (radians; None = zeros) or an integer array (gray levels, taken
+        as they are).  Returns ``display``.  Nothing is written to hardware and nothing sleeps (``settle`` is accepted)."""
+        correct = self.phase_correct if phase_correct is None else phase_correct
+        if hasattr(phase, "get_display"):
+            self.display = phase.get_display(self, phase_correct=bool(correct))
+            self._phase_from = (phase, bool(correct))
+            return self.display
+        if hasattr(phase, "get_phase"):
+            phase = phase.get_phase()
+        given = np.zeros(self.shape) if phase is None else np.asarray(phase)
+        if np.issubdtype(given.dtype, np.integer):
+            if given.dtype != self.dtype:
+                raise TypeError(f"Unexpected integer type {given.dtype}. Expected {self.dtype}.")
+            if np.any(given >= self.bitresolution):
+                raise TypeError(f"Integer data must be within the bitdepth ({self.bitdepth}-bit) of the SLM.")
+            self.display = np.array(given if given.shape == self.shape else _unpad(given, self.shape), dtype=self.dtype)
+            self.phase = 2 * np.pi - self.display * (2 * np.pi / self.phase_scaling / self.bitresolution)
+            return self.display
+        self.display, self.phase = phase_to_gray(self._mask(given, correct), self.bitdepth, self.phase_scaling)
+        return self.display
+
+
+def _unpad(matrix, shape):
+    from ..holography import toolbox
+    if matrix.ndim != 2:
+        raise TypeError(f"Expected a 2D phase, got an array of shape {matrix.shape}")
+    return toolbox.unpad(matrix, shape)

@@ -424,6 +424,37 @@ class Hologram:
         with_kernel = include_propagation and self.propagation_kernel is not None
         return self.phase + (self.propagation_kernel if with_kernel else np.pi)
 
+    def get_display(self, slm=None, *, bitdepth=8, phase_scaling=1.0, phase_correction=None, phase_correct=None,
+                    include_propagation=False, get=True):
+        """
+        What ``slm.set_phase(hologram)`` of the reference sends to the panel -- ``get_phase()`` (:786-811), the wavefront
+        correction (hardware/slms/slm.py:664-681) and ``SLM._phase2gray`` (:695-783) -- formed on the GPU from the phase
+        the engine holds and equal to the reference bit for bit: ``slm_shape`` of uint8 (``bitdepth <= 8``) or uint16, a
+        quarter (half) of the bytes ``get_phase()`` moves for float32.  The host phase is not downloaded and nothing is marked stale.
+
+        An ``slm`` (duck-typed: ``bitdepth``, ``phase_scaling``, ``phase_correct``, ``source.get("phase")`` -- a
+        reference SLM object works) supplies what the keywords otherwise do; ``phase_correct`` given here wins over the
+        SLM's.  The correction is float64 ``slm_shape`` and goes to the device only when it changed (see ``_fingerprint``:
+        the engine keeps the fingerprint of what it holds, so a new engine is sent it again; after an in-place edit the
+        sample cannot see, :meth:`refresh_farfield_inputs` forces the next call to send it).
+        ``get=False`` returns a torch tensor on the GPU (a NumPy array in a process that has not imported torch, as
+        ``get_farfield``).  The drop-in for real hardware is
+        ``real_slm.set_phase(hologram.get_display(real_slm))``: integer data passes ``set_phase`` as it is.
+        There is no CPU route: without a GPU this raises ``HgsError``, like ``optimize``.
+        """
+        if slm is not None:
+            bitdepth, phase_scaling = slm.bitdepth, slm.phase_scaling
+            if phase_correct is None:
+                phase_correct = getattr(slm, "phase_correct", True)
+            if phase_correction is None:
+                phase_correction = (getattr(slm, "source", None) or {}).get("phase")
+        phase_correct = True if phase_correct is None else bool(phase_correct)
+        e = self._get_engine()                       # (a phase assigned on the host goes up first)
+        e.send_display_correction(phase_correction, _fingerprint(phase_correction))
+        out = e.get_display(bitdepth=bitdepth, phase_scaling=phase_scaling, include_propagation=include_propagation,
+                            phase_correct=phase_correct, get=get or "torch" not in sys.modules)      # (as get_farfield)
+        return out[0]
+
     def get_amp(self):
         amplitude = self.amp
         return amplitude
@@ -528,10 +559,12 @@ class Hologram:
 
     def refresh_farfield_inputs(self):
         """Forget the device copies of the source amplitude and propagation kernel the per-shape transform engines hold
-        (get_farfield re-sends them only when the arrays look changed -- see _fingerprint): after an in-place edit that the
-        sample cannot see."""
+        (get_farfield re-sends them only when the arrays look changed -- see _fingerprint), and of the wavefront correction
+        this hologram's engine holds for get_display: after an in-place edit that the sample cannot see."""
         for slot in self.__dict__.get("_ff_engines", {}).values():
             slot["amp"] = slot["kernel"] = None
+        if self._engine is not None:                 # ... and of the wavefront correction get_display adds
+            self._engine.forget_display_correction()
 
     # ---- statistics bookkeeping (_stats.py:118-223) ---------------------------------------------------------
     @staticmethod
@@ -1900,6 +1933,10 @@ class MultiplaneHologram(Hologram):
 
     def _get_engine(self):
         raise RuntimeError("MultiplaneHologram has no engine of its own; its children do")
+
+    def get_display(self, *args, **kwargs):
+        """The phase is shared and the parent holds no propagation kernel: the first child converts it."""
+        return self.holograms[0].get_display(*args, **kwargs)
 
     # ---- meta functionality (_multiplane.py:174-289) -----------------------------------------------------
     def _update_flags(self, method, verbose, feedback, stat_groups, **kwargs):
