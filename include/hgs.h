@@ -301,7 +301,7 @@ int hgs_sync(hgs_engine* e);
  * HGS_TILE2_BLOCKS / HGS_ROW_PREF_BLOCKS, and the A/B switches HGS_ROW_XCD, HGS_COL_XMAP, HGS_ROW_SHIFT, HGS_ROW_SHIFT64, HGS_ROW_PREF,
  * HGS_ROW_PREF_BATCH, HGS_TILE_RULE, HGS_MRAF_SPLIT, HGS_MRAF_SPLIT64, HGS_GH2_MASK, HGS_TILE_LIST, HGS_TILE_SHIFT16, HGS_TILE_NR4,
  * HGS_TILE2, HGS_TILE2_MIN_BATCH, HGS_TILE2_PHASE2, HGS_KEEP_G, HGS_FUSED_SHIFT, HGS_MONO_TAB, HGS_MRAF_PRESUM, HGS_PRESUM_ROWS,
- * HGS_PRESUM_BLOCKS, HGS_EMPTY_COL_LOADS, HGS_EMPTY_COL_INVERSE -- all default to the tuned path;
+ * HGS_PRESUM_BLOCKS, HGS_EMPTY_COL_LOADS, HGS_EMPTY_COL_INVERSE, HGS_EMPTY_COL_FORWARD -- all default to the tuned path;
  * HGS_TRACE_INIT=1 prints where hgs_create spends its time).
  *   HGS_KEEP_G (default 1): the last row launch of a float32 hgs_iterate call leaves G of the next body behind, and the next
  *   call -- or hgs_nearfield2farfield -- on an unchanged phase starts from it.  That G is the loop's own un-rounded phasor
@@ -317,6 +317,12 @@ int hgs_sync(hgs_engine* e);
  *   empty also skips the weight rule and its inverse transform -- the constrained column is exactly zero, so is its inverse --
  *   and writes zeros into H.  The forward transform of every column still runs.  HGS_PHASE and HGS_WEIGHTS are the same bit for
  *   bit; 0 runs every inverse while the flags still go with the launch (the tests' A/B reference).
+ * HGS_OPT_EMPTY_COL_FORWARD (default 1; HGS_EMPTY_COL_FORWARD in the environment): where HGS_OPT_EMPTY_COL_INVERSE acts, an empty
+ *   column is not transformed forward either -- in these launches only the column's own weight rule reads its farfield, and
+ *   that rule is skipped.  A half tile whose two columns are both empty requests no G rows, touches no LDS and passes no
+ *   barrier: it only stores its zeros into H.  Every column of H is still written.  It rests on the inverse skip: with
+ *   HGS_OPT_EMPTY_COL_INVERSE = 0 it does nothing.  hgs_dispatch_read marks the launches that skip with `zero_fwd`.
+ *   HGS_PHASE and HGS_WEIGHTS are the same bit for bit; 0 loads and transforms every column (the tests' A/B reference).
  * HGS_OPT_ROCTX (default 0): roctx ranges (hgs_iterate, hgs_nearfield2farfield, hgs_farfield_constraint,
  *   hgs_farfield2nearfield) for rocprofv3 --marker-trace; the roctx library is dlopen'ed on first use.
  * HGS_OPT_KEEP_PREV_PHASE (default 0): a fused hgs_iterate / hgs_iterate_stats call of ONE iteration that rewrites the
@@ -328,7 +334,7 @@ int hgs_sync(hgs_engine* e);
 enum { HGS_OPT_SPARSE_COLUMNS = 1, HGS_OPT_FORCE_STEPWISE = 2, HGS_OPT_TILE_KERNEL = 3, HGS_OPT_SEPARABLE = 4,
        HGS_OPT_SEPARABLE_MIN_SPOTS = 5, HGS_OPT_ROCTX = 6, HGS_OPT_RUN_KERNELS = 7, HGS_OPT_KEEP_PREV_PHASE = 8,
        HGS_OPT_EMPTY_COL_LOADS = 9, HGS_OPT_SEP_WORKGROUPS = 10,
-       HGS_OPT_EMPTY_COL_INVERSE = 11 };
+       HGS_OPT_EMPTY_COL_INVERSE = 11, HGS_OPT_EMPTY_COL_FORWARD = 12 };
 int hgs_set_option(hgs_engine* e, int option, int value);
 
 /* Timing support for bench.py: per-kernel HIP-event timing on the engine stream. */

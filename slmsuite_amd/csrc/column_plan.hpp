@@ -42,6 +42,8 @@ struct Tuning {
                                 // every column, also of those the scan found empty (the tests' A/B reference)
     int empty_col_inverse = 1;  // HGS_EMPTY_COL_INVERSE=0 / HGS_OPT_EMPTY_COL_INVERSE: ... and runs the rule block and the inverse transform
                                 // of those columns as well (the flags still go with the launch)
+    int empty_col_forward = 1;  // HGS_EMPTY_COL_FORWARD=0 / HGS_OPT_EMPTY_COL_FORWARD: ... and, where the inverse is skipped, loads and
+                                // transforms them forward although nothing reads the result (acts only with empty_col_inverse)
     int sparse = 1;             // HGS_OPT_SPARSE_COLUMNS
     int tile = 1;               // HGS_OPT_TILE_KERNEL (0 forces the per-column kernel at every size: the tests' A/B reference)
 };

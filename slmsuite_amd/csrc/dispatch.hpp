@@ -23,6 +23,7 @@ enum : unsigned {
     DF_COL_FLAGS = 128u, // the column scan's flags go with the launch (ColArgs::col_flags)
     DF_SK_CAP = 256u,    // cgemm_streamk: HGS_OPT_SEP_WORKGROUPS holds the grid below min(2 * #CU, tiles * KT)
     DF_ZERO_INV = 512u,  // col_tile2_kernel with the column flags: empty columns skip rule block and inverse (ColArgs::zero_inv)
+    DF_ZERO_FWD = 1024u, // ... and are neither loaded nor transformed forward; an empty half tile only stores zeros (ColArgs::zero_fwd)
 };
 
 struct DispatchSite {

@@ -60,7 +60,7 @@ thread_local DispatchLog* g_dispatch = nullptr;
 // one line per (kernel instance, run-time flags): "family<P0=v0,...> flag ...\tcount\n".  The argument values come from
 // __PRETTY_FUNCTION__ of dispatch_site<Fam, R, V...>: "... [Fam = hgs::KTile, R = float, V = <4096, 1, 6, false, false, 1, 0>]"
 std::string DispatchLog::text() const {
-    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags", "sk_cap", "zero_inv"};
+    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags", "sk_cap", "zero_inv", "zero_fwd"};
     std::string out;
     for (const Ent& e : v) {
         std::vector<std::string> vals;
@@ -337,6 +337,7 @@ template <typename R> struct Engine : EngineBase {
         t.presum_blocks = env_int("HGS_PRESUM_BLOCKS", 0);
         t.empty_col_loads = env_int("HGS_EMPTY_COL_LOADS", 1);
         t.empty_col_inverse = env_int("HGS_EMPTY_COL_INVERSE", 1);
+        t.empty_col_forward = env_int("HGS_EMPTY_COL_FORWARD", 1);
         return t;
     }
 
@@ -1691,7 +1692,11 @@ template <typename R> struct Engine : EngineBase {
             }
             if (l.listed) { a.col_list = active.list; a.n_active = active.n_dev; }
             a.list_xmap = l.list_xmap ? 1 : 0;
-            if (l.col_flags) { a.col_flags = col_active; a.zero_inv = tun.empty_col_inverse ? 1 : 0; }
+            if (l.col_flags) {
+                a.col_flags = col_active;
+                a.zero_inv = tun.empty_col_inverse ? 1 : 0;
+                a.zero_fwd = (a.zero_inv && tun.empty_col_forward) ? 1 : 0;      // (the forward skip rests on the inverse skip)
+            }
             a.few_active = l.few_active ? 1 : 0;
             if (l.family == ColFamily::tile_split || l.family == ColFamily::tile_split_stats) { a.gh2 = gh2; a.gh2_sparse = l.gh2_sparse ? 1 : 0; }
             LCHK(launch_family(l, a));
@@ -2102,6 +2107,7 @@ template <typename R> struct Engine : EngineBase {
             case HGS_OPT_RUN_KERNELS: comp.opt_run = value ? 1 : 0; return 0;
             case HGS_OPT_EMPTY_COL_LOADS: tun.empty_col_loads = value ? 1 : 0; return 0;
             case HGS_OPT_EMPTY_COL_INVERSE: tun.empty_col_inverse = value ? 1 : 0; return 0;
+            case HGS_OPT_EMPTY_COL_FORWARD: tun.empty_col_forward = value ? 1 : 0; return 0;
             case HGS_OPT_KEEP_PREV_PHASE: opt_prev_phase = value ? 1 : 0; if (!value) state.prev_phase_dropped(); return 0;
             case HGS_OPT_ROCTX:
                 if (value && !g_roctx.load()) return fail(HGS_ERR_UNSUPPORTED, "no roctx library (librocprofiler-sdk-roctx / libroctx64) found");

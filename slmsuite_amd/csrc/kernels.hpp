@@ -16,6 +16,7 @@
 // pass and no index rotation exists; arrays always hold the reference's centred values.
 #pragma once
 #include "fft_core.hpp"
+#include "tile_flags.hpp"
 
 // ---- build switches ------------------------------------------------------------------------------------
 // Everything a build can set from the command line.  None of them is a decision left open: they are numeric tunables and
@@ -1056,6 +1057,8 @@ template <typename R> struct ColArgs {
     int few_active;        // at most a quarter of the farfield columns hold a non-zero weight or target (col_tile2_kernel NXF)
     int zero_inv;          // col_tile2_kernel with col_flags (HGS_OPT_EMPTY_COL_INVERSE): a column whose bit 0 is clear skips the rule
                            // block and its inverse transform -- the constrained column is exactly zero, so is its inverse
+    int zero_fwd;          // ... (HGS_OPT_EMPTY_COL_FORWARD, only with zero_inv) and is neither loaded nor transformed forward: nothing
+                           // reads the farfield of such a column; a half tile of two empty columns only stores its zeros
     int fnr;               // col_fused_kernel: register slots the shifted SLM rows occupy (0 = the unshifted kernel, NRS = 16)
     int fshift;            // col_fused_kernel<..., NRS < 16> (float64, >= 4096 rows): circular shift of the transform input, a
                            // multiple of 16 rows (shift theorem, as in col_tile_kernel): the SLM rows occupy slots 0 .. NRS - 1
@@ -2434,13 +2437,26 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
         constexpr bool TBUF = N == 4096 && PHASE == 0 && (NXF || !PARK);
         static_assert(!NXF || TBUF, "col_tile2_kernel: the instances that request the next half tile ahead take the buffer form");
         float4 tq[TBUF ? NR : 1];
+        // An EMPTY half tile (a.zero_fwd, both scan bytes of the half have bit 0 clear): no rule block reads the farfield of its
+        // columns, the plain instances store neither phase_ff nor amp_ff, inv_fnorm is the nearfield's Parseval constant and H of
+        // an empty column is zero whatever G was -- so its rows are not requested (an empty resource, straight-line like every
+        // other row request: the compiler keeps counting vmcnt), nothing is parked or transformed, no LDS traffic and no barrier:
+        // the half tile only stores the zeros the skipped inverse would have left (below).  A scalar of the flag word and the
+        // arguments, the same in all four waves.
+        bool skip_ht = false;
+        if constexpr (WTBUF && PHASE == 0) skip_ht = cflag4 != nullptr && a.zero_fwd != 0 && tile2_half_empty(fw, half);
         if constexpr (TBUF) {
-            // (rows that already arrived in nq: an empty resource -- nothing is fetched)
-            const Buf bt(gh, (NXF && have_nq) ? 0u : (unsigned)((size_t)g.Sh * 4 - 2 * half) * (unsigned)sizeof(Cx<R>));
+            // (rows that already arrived in nq, or that nobody will read: an empty resource -- nothing is fetched)
+            const Buf bt(gh, ((NXF && have_nq) || skip_ht) ? 0u : (unsigned)((size_t)g.Sh * 4 - 2 * half) * (unsigned)sizeof(Cx<R>));
 #pragma unroll
             for (int m = 0; m < NR; ++m)
                 tq[TBUF ? m : 0] = bt.template ld<float4>((unsigned)(r_lane + m * T) * 4u * (unsigned)sizeof(Cx<R>), 0u);   // (negative rows wrap out of range)
         }
+        const int col0 = ct * 4 + 2 * half;
+        const bool more = ct + ct_step < ntiles;
+        if constexpr (WTBUF) { if (cflag4 != nullptr && more) fwn = uniform_load_i32(cflag4 + ct + ct_step); }
+        float4 outq[PARK ? NR : 1];
+        if (!skip_ht) {
 #pragma unroll
         for (int m = 0; m < NR; ++m) {
             const int r = r_lane + m * T;
@@ -2460,13 +2476,10 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
         HGS_T(fft.tr_n, 2);
-        const int col0 = ct * 4 + 2 * half;
-        const bool more = ct + ct_step < ntiles;
-        if constexpr (WTBUF) { if (cflag4 != nullptr && more) fwn = uniform_load_i32(cflag4 + ct + ct_step); }
         if (first) {
             if (wt_buf)
                 issue_wt_loads_buf<R, T>(wbase + (size_t)col0 * g.Ph, tbase + (size_t)col0 * g.Ph,
-                                         ((fw >> (16 * half)) & 1) ? col_bytes : 0u, do_upd, j, wr, tr);
+                                         tile2_col_active(fw, half, 0) ? col_bytes : 0u, do_upd, j, wr, tr);
             else
                 issue_wt_loads<R, T>(wbase + (size_t)col0 * g.Ph, tbase + (size_t)col0 * g.Ph, do_upd, j, wr, tr);
             first = false;
@@ -2485,6 +2498,20 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                     v[m] = mk<R>(0, 0);
                 }
             }
+            // An EMPTY column (bit 0 of its scan byte clear, a.zero_inv): weight and target are zero in every pixel, every pixel
+            // below would take the wave_all_zero exit and the inverse would transform sixteen zeros per lane.  Both are
+            // skipped; slots 0 .. NR-1 become +0 and the code after the inverse writes them where it writes every column's H.  The
+            // condition is a scalar of the flag word, the same in all four waves: every wave skips the same barriers.
+            // With a.zero_fwd the column is not transformed forward either: only its own rule block would have read the result.
+            // LDS (comment above WgFftL): a forward transform ends with a barrier and writes only the writing wave's own
+            // regions, so the next forward transform may follow it directly, as in col_presum_kernel; a column that is not
+            // transformed at all touches no LDS, and inverse -> forward of the next column is the normal sequence.
+            // The requests for the next column and the weight stores stay outside the branch: both paths reach the head of
+            // the column loop with the same requests in flight.
+            bool empty_col = false;
+            if constexpr (WTBUF && PHASE == 0)
+                empty_col = cflag4 != nullptr && a.zero_inv != 0 && !tile2_col_active(fw, half, c);
+            if (!(empty_col && a.zero_fwd != 0))
             fft.template fwd_lead<(NR < 4 ? 4 : NR)>(v, lds, j);     // slots NR.. are zero (rows outside the SLM)
             HGS_T(fft.tr_n, 3);
 #if HGS_TRACE
@@ -2503,17 +2530,6 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
             const float4* pq = PFQ ? reinterpret_cast<const float4*>(pfc + lane_pos<T>(j, 0)) : nullptr;
             float4 qa = make_float4(0, 0, 0, 0), qb = qa;
             if constexpr (PFQ) { qa = pq[0]; qb = pq[1]; }
-            // An EMPTY column (bit 0 of its scan byte clear, a.zero_inv): weight and target are zero in every pixel, every pixel
-            // below would take the wave_all_zero exit and the inverse would transform sixteen zeros per lane.  Both are
-            // skipped; slots 0 .. NR-1 become +0 and the code after the inverse writes them where it writes every column's H.  The
-            // condition is a scalar of the flag word, the same in all four waves: every wave skips the same barriers.
-            // LDS (comment above WgFftL): the forward transform above ended with a barrier and writes only the writing wave's
-            // own regions, so the next forward transform may follow it directly, as in col_presum_kernel.
-            // The requests for the next column and the weight stores stay outside the branch: both paths reach the head of
-            // the column loop with the same requests in flight.
-            bool empty_col = false;
-            if constexpr (WTBUF && PHASE == 0)
-                empty_col = cflag4 != nullptr && a.zero_inv != 0 && ((fw >> (16 * half + 8 * c)) & 1) == 0;
             if (!empty_col)
             static_for<0, 16>([&](auto m_) {
                 constexpr int m = m_;
@@ -2562,8 +2578,8 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 if (wt_buf) {
                     // (straight-line: no next half tile = an empty resource on this column)
                     const int ncol = c == 0 ? col0 + 1 : more ? (ct + ct_step) * 4 + 2 * half : col0;
-                    const int nflag = c == 0 ? fw >> (16 * half + 8) : more ? fwn >> (16 * half) : 0;
-                    issue_wt_loads_buf<R, T>(wbase + (size_t)ncol * g.Ph, tbase + (size_t)ncol * g.Ph, (nflag & 1) ? col_bytes : 0u,
+                    const bool nact = c == 0 ? tile2_col_active(fw, half, 1) : more && tile2_col_active(fwn, half, 0);
+                    issue_wt_loads_buf<R, T>(wbase + (size_t)ncol * g.Ph, tbase + (size_t)ncol * g.Ph, nact ? col_bytes : 0u,
                                              do_upd, j, wr, tr);
                 } else {
                     const int ncol = c == 0 ? col0 + 1 : (ct + ct_step) * 4 + 2 * half;
@@ -2599,6 +2615,32 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 }
             }
         }
+        if constexpr (PARK) {
+#pragma unroll
+            for (int m = 0; m < NR; ++m) {
+                const Cx<R> h1 = v[m] * (sgs * a.scale);
+                const Cx<R> h0 = park[m * T];
+                outq[m] = make_float4(h0.x, h0.y, h1.x, h1.y);
+            }
+        }
+        } else {
+            // the empty half tile: H of both columns is the +0 of the skipped inverse times the lane's sign and scale, exactly what
+            // the column loop leaves for an empty column; the stores below are the ones every half tile issues
+            const R z = (R)0 * (sgs * a.scale);
+#pragma unroll
+            for (int m = 0; m < NR; ++m) {
+                if constexpr (PARK) outq[m] = make_float4(z, z, z, z);
+                else { g0x[m] = z; g0y[m] = z; g1x[m] = z; g1y[m] = z; }
+            }
+            // The weight / target chain: a half tile enters its column loop with the requests of its first column in flight, from
+            // `first` or from the half tile before it -- here that is this one.  ONE request, for the first column of the
+            // workgroup's next half tile (an empty resource when that column is empty or there is no next half tile), and the
+            // workgroup's first half tile counts as seen.  (skip_ht implies flags, i.e. the resource form of the requests.)
+            const int ncol = more ? (ct + ct_step) * 4 + 2 * half : col0;
+            issue_wt_loads_buf<R, T>(wbase + (size_t)ncol * g.Ph, tbase + (size_t)ncol * g.Ph,
+                                     (more && tile2_col_active(fwn, half, 0)) ? col_bytes : 0u, do_upd, j, wr, tr);
+            first = false;
+        }
         if constexpr (!PARK) {
 #pragma unroll
             for (int m = 0; m < NR; ++m) {
@@ -2607,21 +2649,18 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                     *reinterpret_cast<float4*>(gh + (unsigned)r * 4u) = make_float4(g0x[m], g0y[m], g1x[m], g1y[m]);
             }
         } else {
-            float4 outq[NR];
-#pragma unroll
-            for (int m = 0; m < NR; ++m) {
-                const Cx<R> h1 = v[m] * (sgs * a.scale);
-                const Cx<R> h0 = park[m * T];
-                outq[m] = make_float4(h0.x, h0.y, h1.x, h1.y);
-            }
-            have_nq = NXF && ct + ct_step < ntiles;
+            have_nq = NXF && more;
             if constexpr (NXF) {
                 // straight-line: NR loads through a resource that is empty when there is no next half tile, then NR stores through
                 // one that drops rows outside the SLM -- the compiler can count what is in flight, so the wait for the new rows at
                 // the top of the loop is vmcnt(NR), not vmcnt(0): it no longer includes the acknowledgement of these stores
+                // (a next half tile that is EMPTY reads no rows: its requests go through the empty resource too; have_nq stays
+                //  true, nq then holds zeros nobody reads, and the top of the loop requests nothing either)
+                bool next_empty = false;
+                if constexpr (WTBUF && PHASE == 0) next_empty = cflag4 != nullptr && a.zero_fwd != 0 && tile2_half_empty(fwn, half);
                 const Cx<R>* ghn = a.gh + (size_t)b * g.Sh * g.Pw + (size_t)(have_nq ? ct + ct_step : ct) * g.Sh * 4 + 2 * half;
                 const unsigned tbytes = (unsigned)((size_t)g.Sh * 4 - 2 * half) * (unsigned)sizeof(Cx<R>);
-                const Buf bn(ghn, have_nq ? tbytes : 0u), bs(gh, tbytes);
+                const Buf bn(ghn, (have_nq && !next_empty) ? tbytes : 0u), bs(gh, tbytes);
 #pragma unroll
                 for (int m = 0; m < NR; ++m)
                     nq[NXF ? m : 0] = bn.template ld<float4>((unsigned)(r_lane + m * T) * 4u * (unsigned)sizeof(Cx<R>), 0u);
