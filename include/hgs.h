@@ -249,6 +249,49 @@ int hgs_get_display(hgs_engine* e, const hgs_display_params* p, void* host, size
 /* ... into a caller-provided DEVICE buffer (e.g. a torch tensor); synchronous */
 int hgs_get_display_device(hgs_engine* e, const hgs_display_params* p, void* dev, size_t nbytes);
 
+/* Polynomial phase masks rastered on the device: toolbox.phase.polynomial (phase.py:1672-1795) and zernike_sum (:964-1166).
+ * For n stacked masks over h * w pixels
+ *     out[k][p] = sum over a + b <= degree of table[k][b][a] * xs(p)^a * ys(p)^b  (+ vortex[k] * atan2(ys, xs) where vortex[k] > 0),
+ *     xs = x * x_scale,  ys = y * y_scale,
+ * evaluated in double by Horner's scheme whatever the grid's type and rounded ONCE to the grid's type (grid_bytes).  table
+ * is the dense triangle of monomial coefficients the caller folds its terms and weights into: row b holds the degree - b + 1
+ * coefficients of y^b, a ascending; rows follow each other, (degree + 1)(degree + 2) / 2 doubles per mask.  degree above
+ * HGS_POLY_MAX_DEGREE returns HGS_ERR_UNSUPPORTED.
+ * mask_mode: HGS_POLY_MASK_ZERO / _NAN write 0 / NaN outside  square(x * x_scale) + square(y * y_scale) <= 1, a predicate
+ * evaluated in the grid's own type with every product, square and the sum rounded on its own and the scales rounded to that
+ * type first -- NumPy's arithmetic, so the masked SET is the reference's.
+ * Coordinates: either the two axis vectors of a product grid (x_axis[w], y_axis[h]) or the two full arrays
+ * (x_grid[h][w], y_grid[h][w]; rotated or calibrated grids), host pointers of the grid's type.  Full arrays that turn out to
+ * be a product grid are read as axes.  hgs_dispatch_read shows which form ran: poly_kernel<R=..,OUT_BYTES=..,PROD=..>. */
+enum { HGS_POLY_MASK_NONE = 0, HGS_POLY_MASK_ZERO = 1, HGS_POLY_MASK_NAN = 2 };
+#define HGS_POLY_MAX_DEGREE 20
+typedef struct {
+    int32_t h, w;            /* pixels of one mask                                                     */
+    int32_t n;               /* stacked masks                                                          */
+    int32_t degree;          /* 0 .. HGS_POLY_MAX_DEGREE                                               */
+    int32_t grid_bytes;      /* 4 | 8: type of the coordinates; the values are rounded to it           */
+    int32_t out_bytes;       /* hgs_poly_eval: type the values are stored as, 4 | 8; 0 = grid_bytes     */
+    int32_t mask_mode;       /* HGS_POLY_MASK_*                                                        */
+    int32_t device;          /* hgs_poly_eval: HIP device ordinal                                      */
+    double x_scale, y_scale;
+    const double* table;     /* [n][(degree + 1)(degree + 2) / 2]                                      */
+    const double* vortex;    /* [n], or NULL: no vortex plate                                          */
+    const void* x_axis;      /* [w] and                                                                */
+    const void* y_axis;      /* [h]: a product grid -- or NULL, then                                   */
+    const void* x_grid;      /* [h][w] and                                                             */
+    const void* y_grid;      /* [h][w]                                                                 */
+} hgs_poly_params;
+/* [n][h][w] of out_bytes-sized reals into a host array or, out_is_device != 0, a DEVICE buffer (e.g. a torch tensor) aligned
+ * to its element size; nbytes exactly that.  Needs no engine; synchronous.  Its launches are recorded per thread and read
+ * with hgs_poly_dispatch_read (buffer semantics of hgs_dispatch_read). */
+int hgs_poly_eval(const hgs_poly_params* p, void* out, size_t nbytes, int out_is_device);
+int hgs_poly_dispatch_read(char* buf, size_t nbytes, size_t* needed);
+/* ... into one of the engine's own arrays, nothing passing through the host: HGS_PROP_KERNEL, HGS_PHASE (one mask broadcast
+ * over the batch) in the engine's type, or HGS_DISPLAY_CORRECTION (double).  The values are those hgs_poly_eval gives for
+ * grid_bytes, converted to the array's type -- what uploading that result with hgs_set_array stores.  n must be 1 and
+ * (h, w) the SLM shape (HGS_ERR_ARG otherwise); out_bytes and device are ignored.  Synchronous. */
+int hgs_set_array_poly(hgs_engine* e, int which, const hgs_poly_params* p);
+
 /* MultiplaneHologram._farfield2nearfield (_multiplane.py:255-279): every child runs
  * _farfield2nearfield(extract=False) on its own (constrained) farfield; the children's complex
  * nearfields over the SLM are summed on the device,
@@ -356,7 +399,7 @@ int hgs_iterate_timed(hgs_engine* e, hgs_step* step, int n_iter, double* ms);
  * (family, its template arguments by name -- the ones rocprofv3 prints positionally --, flags list / load_mask /
  * store_mask / xmap / batch / stats / nf_out, launch count).  Families: row_kernel, col_kernel, col_fused_kernel,
  * col_tile_kernel, bluestein_lines, c_n2f_run, c_f2n_run, c_n2f_partial, c_f2n, cgemm_streamk, cg_seed_kernel, cg_adam_kernel,
- * vortex_find_kernel, vortex_remove_kernel, phase_display_kernel
+ * vortex_find_kernel, vortex_remove_kernel, phase_display_kernel, poly_kernel
  * (the small element-wise / reduction helpers are not recorded).  The tests assert it next to the numbers: neighbouring variants often agree to
  * the last bit, so only this shows that a policy reached the kernel it names.  `needed` (optional) receives the bytes
  * the text takes including the terminator; with buf = NULL and nbytes = 0 the call is a size query and keeps the record,

@@ -54,6 +54,15 @@ class hgs_display_params(C.Structure):
                [(n, C.c_int32) for n in ("bitdepth", "include_propagation", "phase_correct", "reserved")]
 
 
+class hgs_poly_params(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("h", "w", "n", "degree", "grid_bytes", "out_bytes", "mask_mode", "device")] + \
+               [("x_scale", C.c_double), ("y_scale", C.c_double)] + \
+               [(n, C.c_void_p) for n in ("table", "vortex", "x_axis", "y_axis", "x_grid", "y_grid")]
+
+
+POLY_MASK_NONE, POLY_MASK_ZERO, POLY_MASK_NAN = 0, 1, 2
+POLY_MAX_DEGREE = 20
+
 _lib = None
 
 
@@ -123,6 +132,9 @@ def load():
         "hgs_remove_vortices": (C.c_int, [eng, P(C.c_int32)]),
         "hgs_get_display": (C.c_int, [eng, P(hgs_display_params), C.c_void_p, C.c_size_t]),
         "hgs_get_display_device": (C.c_int, [eng, P(hgs_display_params), C.c_void_p, C.c_size_t]),
+        "hgs_poly_eval": (C.c_int, [P(hgs_poly_params), C.c_void_p, C.c_size_t, C.c_int]),
+        "hgs_poly_dispatch_read": (C.c_int, [C.c_char_p, C.c_size_t, P(C.c_size_t)]),
+        "hgs_set_array_poly": (C.c_int, [eng, C.c_int, P(hgs_poly_params)]),
         "hgs_sync": (C.c_int, [eng]),
         "hgs_set_option": (C.c_int, [eng, C.c_int, C.c_int]),
         "hgs_profile_enable": (C.c_int, [eng, C.c_int]),
@@ -142,8 +154,21 @@ def load():
 
 EXPORTS = ("hgs_create", "hgs_destroy", "hgs_set_array", "hgs_get_array", "hgs_get_array_device", "hgs_set_array_device", "hgs_copy_phase",
            "hgs_reset_weights", "hgs_reset", "hgs_set_array_sparse", "hgs_nearfield2farfield", "hgs_farfield_constraint",
-           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_cg_iterate", "hgs_remove_vortices", "hgs_get_display", "hgs_get_display_device", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
+           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_cg_iterate", "hgs_remove_vortices", "hgs_get_display", "hgs_get_display_device", "hgs_poly_eval", "hgs_poly_dispatch_read", "hgs_set_array_poly", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
            "hgs_profile_read", "hgs_iterate_timed", "hgs_dispatch_read", "hgs_last_error", "hgs_version")
+
+
+def parse_dispatch(text):
+    """The lines of a dispatch record (hgs_dispatch_read, hgs_poly_dispatch_read) as a list of
+    ``{"kernel": family, "args": {template parameter: value}, "flags": set, "count": launches, "name": text}``."""
+    out = []
+    for line in text.splitlines():
+        name, count = line.rsplit("\t", 1)
+        head, _, flags = name.partition("> ")
+        family, _, arglist = head.rstrip(">").partition("<")
+        args = dict(kv.split("=", 1) for kv in arglist.split(",") if kv)
+        out.append({"kernel": family, "args": args, "flags": set(flags.split()), "count": int(count), "name": name})
+    return out
 
 
 def check(code):

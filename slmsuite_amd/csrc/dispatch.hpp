@@ -74,6 +74,7 @@ HGS_FAMILY(KCgAdam, "cg_adam_kernel", "R");
 HGS_FAMILY(KVortexFind, "vortex_find_kernel", "R");
 HGS_FAMILY(KVortexRemove, "vortex_remove_kernel", "R");
 HGS_FAMILY(KDisplay, "phase_display_kernel", "R,BITS");
+HGS_FAMILY(KPoly, "poly_kernel", "R,OUT_BYTES,PROD");
 #undef HGS_FAMILY
 
 }  // namespace hgs

@@ -22,6 +22,7 @@
 #include "cg_kernels.hpp"
 #include "vortex_kernels.hpp"
 #include "display_kernels.hpp"
+#include "poly_kernels.hpp"
 #include <complex>
 #include <dlfcn.h>
 
@@ -129,6 +130,87 @@ struct ColList {
     }
 };
 
+// ---- polynomial phase masks (include/hgs.h, poly_kernels.hpp) ------------------------------------------------------------
+// the launches of hgs_poly_eval, which has no engine to keep them
+static thread_local DispatchLog g_poly_log;
+
+static int poly_check(const hgs_poly_params* p) {
+    if (!p) return fail(HGS_ERR_ARG, "null parameters");
+    if (p->h < 1 || p->w < 1 || p->n < 1) return fail(HGS_ERR_ARG, "polynomial mask: h, w and n must be positive (got %d, %d, %d)", p->h, p->w, p->n);
+    if (p->degree < 0) return fail(HGS_ERR_ARG, "polynomial mask: negative degree %d", p->degree);
+    if (p->degree > HGS_POLY_MAX_DEGREE)
+        return fail(HGS_ERR_UNSUPPORTED, "polynomial mask: degree %d is beyond the limit of %d", p->degree, HGS_POLY_MAX_DEGREE);
+    if (p->grid_bytes != 4 && p->grid_bytes != 8) return fail(HGS_ERR_ARG, "polynomial mask: grid_bytes must be 4 or 8 (got %d)", p->grid_bytes);
+    if (p->mask_mode < HGS_POLY_MASK_NONE || p->mask_mode > HGS_POLY_MASK_NAN) return fail(HGS_ERR_ARG, "polynomial mask: unknown mask mode %d", p->mask_mode);
+    if (!std::isfinite(p->x_scale) || !std::isfinite(p->y_scale)) return fail(HGS_ERR_ARG, "polynomial mask: the scales must be finite");
+    if (!p->table) return fail(HGS_ERR_ARG, "polynomial mask: null coefficient table");
+    const bool axes = p->x_axis && p->y_axis, grids = p->x_grid && p->y_grid;
+    if (!axes && !grids) return fail(HGS_ERR_ARG, "polynomial mask: needs both axis vectors or both grid arrays");
+    return 0;
+}
+
+// what a launch reads, on the device: the triangle, the vortex weights, the coordinates
+template <typename G> struct PolyDevice {
+    DevBuf<double> table, vortex;
+    DevBuf<G> x, y;
+    bool product = false;
+    int upload(const hgs_poly_params* p, hipStream_t stream) {
+        const size_t T = (size_t)poly_table_len(p->degree), S = (size_t)p->h * p->w;
+        HIPCHK(table.alloc((size_t)p->n * T));
+        HIPCHK(hipMemcpyAsync(table, p->table, (size_t)p->n * T * sizeof(double), hipMemcpyHostToDevice, stream));
+        bool any_vortex = false;
+        for (int k = 0; p->vortex && k < p->n; ++k) any_vortex = any_vortex || p->vortex[k] > 0;
+        if (any_vortex) {
+            HIPCHK(vortex.alloc((size_t)p->n));
+            HIPCHK(hipMemcpyAsync(vortex, p->vortex, (size_t)p->n * sizeof(double), hipMemcpyHostToDevice, stream));
+        }
+        std::vector<G> ax, ay;          // axes found in full arrays; alive until the copies below have landed
+        const G* hx = static_cast<const G*>(p->x_axis);
+        const G* hy = static_cast<const G*>(p->y_axis);
+        product = hx && hy;
+        if (!product) {
+            std::vector<double> dx, dy;
+            product = product_grid_axis(static_cast<const G*>(p->x_grid), p->h, p->w, 0, dx) &&
+                      product_grid_axis(static_cast<const G*>(p->y_grid), p->h, p->w, 1, dy);
+            if (product) {
+                ax.assign(dx.begin(), dx.end()); ay.assign(dy.begin(), dy.end());     // (exact: they were widened from G)
+                hx = ax.data(); hy = ay.data();
+            } else {
+                hx = static_cast<const G*>(p->x_grid); hy = static_cast<const G*>(p->y_grid);
+            }
+        }
+        const size_t nx = product ? (size_t)p->w : S, ny = product ? (size_t)p->h : S;
+        HIPCHK(x.alloc(nx)); HIPCHK(y.alloc(ny));
+        HIPCHK(hipMemcpyAsync(x, hx, nx * sizeof(G), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(y, hy, ny * sizeof(G), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+    int launch(const hgs_poly_params* p, void* dev_out, int out_bytes, hipStream_t stream) const {
+        PolyArgs<G, void> a{};
+        a.out = dev_out; a.x = x; a.y = y; a.table = table; a.vortex = vortex;
+        a.S = (size_t)p->h * p->w; a.W = p->w; a.deg = p->degree; a.mask_mode = p->mask_mode;
+        // the scales meet the grid in ITS type (a Python float times a float32 array is a float32 product)
+        a.x_scale = (double)(G)p->x_scale; a.y_scale = (double)(G)p->y_scale;
+        LCHK(launch_poly<G>(p->n, product, out_bytes, stream, a));
+        return 0;
+    }
+};
+
+// checked parameters -> dev_out ([n][h][w] of out_bytes-sized reals, aligned to out_bytes); wrap(launch) runs the launch
+// (the engine times it there); complete on return
+template <typename G, typename W> static int poly_run_as(const hgs_poly_params* p, void* dev_out, int out_bytes, hipStream_t stream, W&& wrap) {
+    PolyDevice<G> d;
+    if (int e = d.upload(p, stream)) return e;
+    if (int e = wrap([&]() -> int { return d.launch(p, dev_out, out_bytes, stream); })) return e;
+    HIPCHK(hipStreamSynchronize(stream));        // (the buffers of d go with this scope)
+    return 0;
+}
+template <typename W> static int poly_run(const hgs_poly_params* p, void* dev_out, int out_bytes, hipStream_t stream, W&& wrap) {
+    return p->grid_bytes == 4 ? poly_run_as<float>(p, dev_out, out_bytes, stream, wrap)
+                              : poly_run_as<double>(p, dev_out, out_bytes, stream, wrap);
+}
+
 struct EngineBase {
     int device = 0;      // HIP device ordinal of this engine; every C-ABI entry makes it current first
     DispatchLog dispatch;    // kernel instances launched since the last hgs_dispatch_read
@@ -163,6 +245,7 @@ struct EngineBase {
     virtual int cg_iterate(const hgs_cg_params* p, int n, double* loss_out) = 0;
     virtual int remove_vortices(int32_t* n_removed) = 0;
     virtual int get_display(const hgs_display_params* p, void* dst, size_t nbytes, bool dst_device) = 0;
+    virtual int set_array_poly(int which, const hgs_poly_params* p) = 0;
 };
 
 template <typename R> struct Engine : EngineBase {
@@ -1387,6 +1470,40 @@ template <typename R> struct Engine : EngineBase {
         return d2h(dst, disp_out, all, dst_device);
     }
 
+    // hgs_set_array_poly: one polynomial mask rastered into the kernel, the phase or the display correction, on the device
+    int set_array_poly(int which, const hgs_poly_params* p) override {
+        RoctxRange range(opt_roctx, "hgs_set_array_poly");
+        if (which != HGS_PROP_KERNEL && which != HGS_PHASE && which != HGS_DISPLAY_CORRECTION)
+            return fail(HGS_ERR_ARG, "hgs_set_array_poly fills HGS_PROP_KERNEL, HGS_PHASE or HGS_DISPLAY_CORRECTION (got selector %d)", which);
+        if (int e_ = poly_check(p)) return e_;
+        if (p->n != 1) return fail(HGS_ERR_ARG, "hgs_set_array_poly: one mask expected (n = %d)", p->n);
+        if (p->h != cfg.slm_h || p->w != cfg.slm_w)
+            return fail(HGS_ERR_ARG, "hgs_set_array_poly: mask of shape (%d, %d) is not of the SLM shape (%d, %d)", p->h, p->w, cfg.slm_h, cfg.slm_w);
+        auto run = [&](void* dst, int out_bytes) -> int {
+            return poly_run(p, dst, out_bytes, stream, [&](auto&& launch) -> int { return timed(HGS_K_ELEMENTWISE, launch); });
+        };
+        if (which == HGS_DISPLAY_CORRECTION) {               // not a nearfield input: the loop never sees it
+            HIPCHK(disp_corr.ensure(S));
+            has_disp_corr = false;
+            if (int e_ = run(disp_corr.get(), (int)sizeof(double))) return e_;
+            has_disp_corr = true;
+            return 0;
+        }
+        state.nearfield_upload_begins();
+        if (which == HGS_PROP_KERNEL) {
+            HIPCHK(kern.ensure(S));
+            if (int e_ = run(kern.get(), (int)sizeof(R))) return e_;
+            has_kern = true;
+        } else {
+            if (int e_ = run(phase.get(), (int)sizeof(R))) return e_;
+            for (int b = 1; b < B; ++b)
+                HIPCHK(hipMemcpyAsync(phase + (size_t)b * S, phase.get(), S * sizeof(R), hipMemcpyDeviceToDevice, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        state.nearfield_input_changed();
+        return 0;
+    }
+
     int mp_info(MpInfo* o) override {
         o->nf = nfbuf; o->kern = has_kern ? kern : nullptr; o->phase = phase; o->S = S; o->B = B;
         o->real_bytes = (int)sizeof(R); o->device = cfg.device; o->stream = stream;
@@ -2278,9 +2395,8 @@ int hgs_iterate_timed(hgs_engine* e, hgs_step* step, int n_iter, double* ms) {
     return e->impl->iterate_timed(step, n_iter, ms);
 }
 
-int hgs_dispatch_read(hgs_engine* e, char* buf, size_t nbytes, size_t* needed) {
-    if (!e || !e->impl) return hgs::fail(HGS_ERR_ARG, "null engine handle");
-    const std::string t = e->impl->dispatch.text();
+static int dispatch_text_out(hgs::DispatchLog& log, char* buf, size_t nbytes, size_t* needed) {
+    const std::string t = log.text();
     if (needed) *needed = t.size() + 1;
     if (!buf || nbytes < t.size() + 1) {
         if (buf && nbytes) buf[0] = 0;
@@ -2288,7 +2404,37 @@ int hgs_dispatch_read(hgs_engine* e, char* buf, size_t nbytes, size_t* needed) {
         return hgs::fail(HGS_ERR_ARG, "dispatch record needs %zu bytes", t.size() + 1);
     }
     std::memcpy(buf, t.c_str(), t.size() + 1);
-    e->impl->dispatch.v.clear();
+    log.v.clear();
+    return 0;
+}
+
+int hgs_dispatch_read(hgs_engine* e, char* buf, size_t nbytes, size_t* needed) {
+    if (!e || !e->impl) return hgs::fail(HGS_ERR_ARG, "null engine handle");
+    return dispatch_text_out(e->impl->dispatch, buf, nbytes, needed);
+}
+
+int hgs_poly_dispatch_read(char* buf, size_t nbytes, size_t* needed) { return dispatch_text_out(hgs::g_poly_log, buf, nbytes, needed); }
+
+int hgs_set_array_poly(hgs_engine* e, int which, const hgs_poly_params* p) { ENG(e) return e->impl->set_array_poly(which, p); }
+
+int hgs_poly_eval(const hgs_poly_params* p, void* out, size_t nbytes, int out_is_device) {
+    if (int r = hgs::poly_check(p)) return r;
+    if (!out) return hgs::fail(HGS_ERR_ARG, "null destination pointer");
+    const int out_bytes = p->out_bytes ? p->out_bytes : p->grid_bytes;
+    if (out_bytes != 4 && out_bytes != 8) return hgs::fail(HGS_ERR_ARG, "hgs_poly_eval: out_bytes must be 0, 4 or 8 (got %d)", p->out_bytes);
+    const size_t all = (size_t)p->n * p->h * p->w * out_bytes;
+    if (nbytes != all)
+        return hgs::fail(HGS_ERR_ARG, "hgs_poly_eval: bad size %zu (%zu expected: %d masks of %d x %d %d-byte reals)", nbytes, all, p->n, p->h, p->w, out_bytes);
+    if (out_is_device && ((uintptr_t)out % (uintptr_t)out_bytes))
+        return hgs::fail(HGS_ERR_ARG, "hgs_poly_eval: the device buffer is not aligned to its %d-byte elements", out_bytes);
+    hgs::DeviceGuard guard_(p->device, &hgs::g_poly_log);
+    if (!guard_.ok) return hgs::fail(HGS_ERR_DEVICE, "hipSetDevice(%d) failed", p->device);
+    auto plain = [](auto&& launch) -> int { return launch(); };
+    if (out_is_device) return hgs::poly_run(p, out, out_bytes, nullptr, plain);
+    hgs::DevBuf<char> tmp;
+    if (tmp.alloc(all) != hipSuccess) return hgs::fail(HGS_ERR_DEVICE, "hgs_poly_eval: no device memory for %zu bytes", all);
+    if (int r = hgs::poly_run(p, tmp.get(), out_bytes, nullptr, plain)) return r;
+    if (hipMemcpy(out, tmp.get(), all, hipMemcpyDeviceToHost) != hipSuccess) return hgs::fail(HGS_ERR_DEVICE, "hgs_poly_eval: device to host copy failed");
     return 0;
 }
 

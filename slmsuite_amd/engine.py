@@ -226,12 +226,23 @@ class Engine:
         L.check(self.lib.hgs_get_array(self._h, L.VORTICES, out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
 
+    def set_array_poly(self, which, mask):
+        """hgs_set_array_poly: a ``toolbox.phase.PolynomialMask`` (one mask of ``slm_shape``) rastered on the device into
+        ``PROP_KERNEL``, ``PHASE`` or ``DISPLAY_CORRECTION``; nothing SLM-sized exists on the host."""
+        prm, keep = mask.params(device=self.device)
+        L.check(self.lib.hgs_set_array_poly(self._h, int(which), C.byref(prm)))
+        del keep
+
     def set_display_correction(self, arr):
         """HGS_DISPLAY_CORRECTION: the wavefront correction ``get_display`` adds (``slm.source["phase"]``), ``slm_shape``,
-        held as float64 whatever the engine's precision; ``None`` clears it."""
+        held as float64 whatever the engine's precision; ``None`` clears it.  A ``toolbox.phase.PolynomialMask`` is formed
+        on the device (``set_array_poly``)."""
         self._display_fp = self._NOT_SENT
         if arr is None:
             L.check(self.lib.hgs_set_array(self._h, L.DISPLAY_CORRECTION, None, 0))
+            return
+        if hasattr(arr, "params") and hasattr(arr, "fingerprint"):
+            self.set_array_poly(L.DISPLAY_CORRECTION, arr)
             return
         a = np.ascontiguousarray(arr, dtype=np.float64)
         if a.shape != self.slm_shape:
@@ -320,14 +331,7 @@ class Engine:
         L.check(self.lib.hgs_dispatch_read(self._h, None, 0, C.byref(need)))
         buf = C.create_string_buffer(max(1, need.value))
         L.check(self.lib.hgs_dispatch_read(self._h, buf, len(buf), None))
-        out = []
-        for line in buf.value.decode().splitlines():
-            name, count = line.rsplit("\t", 1)
-            head, _, flags = name.partition("> ")
-            family, _, arglist = head.rstrip(">").partition("<")
-            args = dict(kv.split("=", 1) for kv in arglist.split(",") if kv)
-            out.append({"kernel": family, "args": args, "flags": set(flags.split()), "count": int(count), "name": name})
-        return out
+        return L.parse_dispatch(buf.value.decode())
 
     def version(self):
         return self.lib.hgs_version().decode()
