@@ -292,6 +292,59 @@ int hgs_poly_dispatch_read(char* buf, size_t nbytes, size_t* needed);
  * (h, w) the SLM shape (HGS_ERR_ARG otherwise); out_bytes and device are ignored.  Synchronous. */
 int hgs_set_array_poly(hgs_engine* e, int which, const hgs_poly_params* p);
 
+/* The masks of toolbox.phase that are no polynomials, rastered on the device (csrc/pattern_kernels.hpp): sinusoid and binary
+ * gratings (phase.py:78-258), the four-window masks built from gratings (quadrants, bahtinov; :261-389), axicon (:455-498),
+ * Laguerre-Gauss and Hermite-Gauss mode masks (:1842-1935).
+ *   HGS_PATTERN_BLAZE     2 pi (vx x + vy y)                                        (quad only: a plain blaze is a polynomial)
+ *   HGS_PATTERN_SINUSOID  (a - b) / 2 * (1 + sin(2 pi (vx x + vy y) + shift)) + b
+ *   HGS_PATTERN_BINARY    a where d > 0 or |d| <= 1e-8, else b, with d = mod(2 pi (vx x + vy y) + shift, 2 pi), set to 0 where
+ *                         isclose(d, 2 pi), less 2 pi (1 - duty); duty is clipped to [0, 1].  A vector with a component
+ *                         above 1 in magnitude counts PIXELS: the coordinates are the pixel indices (within the window, for
+ *                         quad) and each component is replaced by its reciprocal (0 stays 0).  A zero vector gives b, or a
+ *                         when shift != 0 and mod(shift, 2 pi) > 2 pi duty.  d is formed with NumPy's roundings in the
+ *                         grid's type, or in double with decision_double != 0 (vectors that came as float64 scalars) and
+ *                         wherever pixels are counted.
+ *   HGS_PATTERN_AXICON    2 pi sqrt((x kx)^2 + (y ky)^2), (kx, ky) = vec[0..1]; 2 pi k |x| or 2 pi k |y| where the other is 0
+ *   HGS_PATTERN_LG        l atan2(x, y) + pi [L_p^|l|(16 (x^2 + y^2) / w^2) < 0], each term only for l != 0 / p != 0
+ *   HGS_PATTERN_HG        pi where H_n(4 x / w) H_m(4 y / w) > 0, else 0
+ * quad != 0 (grating modes): four windows that start at row h / 2 and column w / 2, in the order top-right, bottom-right,
+ * top-left, bottom-left, each with its own vector vec[2 i], vec[2 i + 1]; the last row and the last column are 0 (the
+ * reference clips the end of a window to h - 1 and w - 1).  Otherwise vec[0..1] alone counts.
+ * Values are formed in double; round_grid != 0 rounds them to the grid's type before they are stored as out_bytes-sized
+ * reals.  Orders p, n, m above HGS_PATTERN_MAX_ORDER return HGS_ERR_UNSUPPORTED, other bad arguments HGS_ERR_ARG.
+ * Coordinates as in hgs_poly_params.  The dispatch record shows pattern_kernel<R=..,OUT_BYTES=..,PROD=..,MODE=..> [quad]. */
+enum { HGS_PATTERN_BLAZE = 0, HGS_PATTERN_SINUSOID = 1, HGS_PATTERN_BINARY = 2, HGS_PATTERN_AXICON = 3, HGS_PATTERN_LG = 4,
+       HGS_PATTERN_HG = 5 };
+#define HGS_PATTERN_MAX_ORDER 20
+typedef struct {
+    int32_t h, w;            /* pixels of the mask                                                      */
+    int32_t grid_bytes;      /* 4 | 8: type of the coordinates                                          */
+    int32_t out_bytes;       /* hgs_pattern_eval: type the values are stored as, 4 | 8; 0 = grid_bytes  */
+    int32_t device;          /* hgs_pattern_eval: HIP device ordinal                                    */
+    int32_t mode;            /* HGS_PATTERN_*                                                           */
+    int32_t quad;            /* grating modes: four windows                                             */
+    int32_t round_grid;      /* round the values to the grid's type                                     */
+    int32_t decision_double; /* HGS_PATTERN_BINARY: form d in double                                    */
+    int32_t l, p, n, m;      /* HGS_PATTERN_LG: l, p;  HGS_PATTERN_HG: n, m                             */
+    int32_t reserved;
+    double vec[8];           /* up to four 2-vectors                                                    */
+    double shift, a, b, duty;
+    double radius;           /* w of the mode masks: the source radius, finite and not 0                */
+    const void* x_axis;      /* as in hgs_poly_params                                                   */
+    const void* y_axis;
+    const void* x_grid;
+    const void* y_grid;
+} hgs_pattern_params;
+/* [h][w] of out_bytes-sized reals into a host array or, out_is_device != 0, a DEVICE buffer aligned to its element size;
+ * nbytes exactly that.  Needs no engine; synchronous.  Its launch joins the per-thread record hgs_poly_dispatch_read reads;
+ * hgs_pattern_dispatch_read reads that same record. */
+int hgs_pattern_eval(const hgs_pattern_params* p, void* out, size_t nbytes, int out_is_device);
+int hgs_pattern_dispatch_read(char* buf, size_t nbytes, size_t* needed);
+/* ... into HGS_PROP_KERNEL, HGS_PHASE (broadcast over the batch) or HGS_DISPLAY_CORRECTION (double) on the engine's stream,
+ * by the rules of hgs_set_array_poly: (h, w) must be the SLM shape, the values are those of hgs_pattern_eval (with
+ * out_bytes = 8) converted to the array's type; out_bytes and device are ignored.  Synchronous. */
+int hgs_set_array_pattern(hgs_engine* e, int which, const hgs_pattern_params* p);
+
 /* MultiplaneHologram._farfield2nearfield (_multiplane.py:255-279): every child runs
  * _farfield2nearfield(extract=False) on its own (constrained) farfield; the children's complex
  * nearfields over the SLM are summed on the device,
@@ -399,7 +452,7 @@ int hgs_iterate_timed(hgs_engine* e, hgs_step* step, int n_iter, double* ms);
  * (family, its template arguments by name -- the ones rocprofv3 prints positionally --, flags list / load_mask /
  * store_mask / xmap / batch / stats / nf_out, launch count).  Families: row_kernel, col_kernel, col_fused_kernel,
  * col_tile_kernel, bluestein_lines, c_n2f_run, c_f2n_run, c_n2f_partial, c_f2n, cgemm_streamk, cg_seed_kernel, cg_adam_kernel,
- * vortex_find_kernel, vortex_remove_kernel, phase_display_kernel, poly_kernel
+ * vortex_find_kernel, vortex_remove_kernel, phase_display_kernel, poly_kernel, pattern_kernel
  * (the small element-wise / reduction helpers are not recorded).  The tests assert it next to the numbers: neighbouring variants often agree to
  * the last bit, so only this shows that a policy reached the kernel it names.  `needed` (optional) receives the bytes
  * the text takes including the terminator; with buf = NULL and nbytes = 0 the call is a size query and keeps the record,

@@ -63,6 +63,17 @@ class hgs_poly_params(C.Structure):
 POLY_MASK_NONE, POLY_MASK_ZERO, POLY_MASK_NAN = 0, 1, 2
 POLY_MAX_DEGREE = 20
 
+
+class hgs_pattern_params(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("h", "w", "grid_bytes", "out_bytes", "device", "mode", "quad", "round_grid",
+                                         "decision_double", "l", "p", "n", "m", "reserved")] + \
+               [("vec", C.c_double * 8)] + [(n, C.c_double) for n in ("shift", "a", "b", "duty", "radius")] + \
+               [(n, C.c_void_p) for n in ("x_axis", "y_axis", "x_grid", "y_grid")]
+
+
+PATTERN_BLAZE, PATTERN_SINUSOID, PATTERN_BINARY, PATTERN_AXICON, PATTERN_LG, PATTERN_HG = range(6)
+PATTERN_MAX_ORDER = 20
+
 _lib = None
 
 
@@ -135,6 +146,9 @@ def load():
         "hgs_poly_eval": (C.c_int, [P(hgs_poly_params), C.c_void_p, C.c_size_t, C.c_int]),
         "hgs_poly_dispatch_read": (C.c_int, [C.c_char_p, C.c_size_t, P(C.c_size_t)]),
         "hgs_set_array_poly": (C.c_int, [eng, C.c_int, P(hgs_poly_params)]),
+        "hgs_pattern_eval": (C.c_int, [P(hgs_pattern_params), C.c_void_p, C.c_size_t, C.c_int]),
+        "hgs_pattern_dispatch_read": (C.c_int, [C.c_char_p, C.c_size_t, P(C.c_size_t)]),
+        "hgs_set_array_pattern": (C.c_int, [eng, C.c_int, P(hgs_pattern_params)]),
         "hgs_sync": (C.c_int, [eng]),
         "hgs_set_option": (C.c_int, [eng, C.c_int, C.c_int]),
         "hgs_profile_enable": (C.c_int, [eng, C.c_int]),
@@ -154,7 +168,7 @@ def load():
 
 EXPORTS = ("hgs_create", "hgs_destroy", "hgs_set_array", "hgs_get_array", "hgs_get_array_device", "hgs_set_array_device", "hgs_copy_phase",
            "hgs_reset_weights", "hgs_reset", "hgs_set_array_sparse", "hgs_nearfield2farfield", "hgs_farfield_constraint",
-           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_cg_iterate", "hgs_remove_vortices", "hgs_get_display", "hgs_get_display_device", "hgs_poly_eval", "hgs_poly_dispatch_read", "hgs_set_array_poly", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
+           "hgs_farfield2nearfield", "hgs_iterate", "hgs_iterate_stats", "hgs_cg_iterate", "hgs_remove_vortices", "hgs_get_display", "hgs_get_display_device", "hgs_poly_eval", "hgs_poly_dispatch_read", "hgs_set_array_poly", "hgs_pattern_eval", "hgs_pattern_dispatch_read", "hgs_set_array_pattern", "hgs_stats", "hgs_multiplane_farfield2nearfield", "hgs_set_option", "hgs_sync", "hgs_profile_enable",
            "hgs_profile_read", "hgs_iterate_timed", "hgs_dispatch_read", "hgs_last_error", "hgs_version")
 
 

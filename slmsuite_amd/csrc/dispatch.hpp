@@ -24,6 +24,7 @@ enum : unsigned {
     DF_SK_CAP = 256u,    // cgemm_streamk: HGS_OPT_SEP_WORKGROUPS holds the grid below min(2 * #CU, tiles * KT)
     DF_ZERO_INV = 512u,  // col_tile2_kernel with the column flags: empty columns skip rule block and inverse (ColArgs::zero_inv)
     DF_ZERO_FWD = 1024u, // ... and are neither loaded nor transformed forward; an empty half tile only stores zeros (ColArgs::zero_fwd)
+    DF_QUAD = 2048u,     // pattern_kernel: four windows, each with its own grating (PatArgs::quad)
 };
 
 struct DispatchSite {
@@ -75,6 +76,7 @@ HGS_FAMILY(KVortexFind, "vortex_find_kernel", "R");
 HGS_FAMILY(KVortexRemove, "vortex_remove_kernel", "R");
 HGS_FAMILY(KDisplay, "phase_display_kernel", "R,BITS");
 HGS_FAMILY(KPoly, "poly_kernel", "R,OUT_BYTES,PROD");
+HGS_FAMILY(KPattern, "pattern_kernel", "R,OUT_BYTES,PROD,MODE");
 #undef HGS_FAMILY
 
 }  // namespace hgs

@@ -23,6 +23,7 @@
 #include "vortex_kernels.hpp"
 #include "display_kernels.hpp"
 #include "poly_kernels.hpp"
+#include "pattern_kernels.hpp"
 #include <complex>
 #include <dlfcn.h>
 
@@ -61,7 +62,7 @@ thread_local DispatchLog* g_dispatch = nullptr;
 // one line per (kernel instance, run-time flags): "family<P0=v0,...> flag ...\tcount\n".  The argument values come from
 // __PRETTY_FUNCTION__ of dispatch_site<Fam, R, V...>: "... [Fam = hgs::KTile, R = float, V = <4096, 1, 6, false, false, 1, 0>]"
 std::string DispatchLog::text() const {
-    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags", "sk_cap", "zero_inv", "zero_fwd"};
+    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags", "sk_cap", "zero_inv", "zero_fwd", "quad"};
     std::string out;
     for (const Ent& e : v) {
         std::vector<std::string> vals;
@@ -149,13 +150,43 @@ static int poly_check(const hgs_poly_params* p) {
     return 0;
 }
 
+// the coordinates of a mask on the device: the two axis vectors of a product grid (given, or found in full arrays), else the
+// two full arrays; complete on return
+template <typename G> struct GridDevice {
+    DevBuf<G> x, y;
+    bool product = false;
+    int upload(const void* x_axis, const void* y_axis, const void* x_grid, const void* y_grid, int h, int w, hipStream_t stream) {
+        const size_t S = (size_t)h * w;
+        std::vector<G> ax, ay;          // axes found in full arrays; alive until the copies below have landed
+        const G* hx = static_cast<const G*>(x_axis);
+        const G* hy = static_cast<const G*>(y_axis);
+        product = hx && hy;
+        if (!product) {
+            std::vector<double> dx, dy;
+            product = product_grid_axis(static_cast<const G*>(x_grid), h, w, 0, dx) &&
+                      product_grid_axis(static_cast<const G*>(y_grid), h, w, 1, dy);
+            if (product) {
+                ax.assign(dx.begin(), dx.end()); ay.assign(dy.begin(), dy.end());     // (exact: they were widened from G)
+                hx = ax.data(); hy = ay.data();
+            } else {
+                hx = static_cast<const G*>(x_grid); hy = static_cast<const G*>(y_grid);
+            }
+        }
+        const size_t nx = product ? (size_t)w : S, ny = product ? (size_t)h : S;
+        HIPCHK(x.alloc(nx)); HIPCHK(y.alloc(ny));
+        HIPCHK(hipMemcpyAsync(x, hx, nx * sizeof(G), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(y, hy, ny * sizeof(G), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return 0;
+    }
+};
+
 // what a launch reads, on the device: the triangle, the vortex weights, the coordinates
 template <typename G> struct PolyDevice {
     DevBuf<double> table, vortex;
-    DevBuf<G> x, y;
-    bool product = false;
+    GridDevice<G> grid;
     int upload(const hgs_poly_params* p, hipStream_t stream) {
-        const size_t T = (size_t)poly_table_len(p->degree), S = (size_t)p->h * p->w;
+        const size_t T = (size_t)poly_table_len(p->degree);
         HIPCHK(table.alloc((size_t)p->n * T));
         HIPCHK(hipMemcpyAsync(table, p->table, (size_t)p->n * T * sizeof(double), hipMemcpyHostToDevice, stream));
         bool any_vortex = false;
@@ -164,35 +195,15 @@ template <typename G> struct PolyDevice {
             HIPCHK(vortex.alloc((size_t)p->n));
             HIPCHK(hipMemcpyAsync(vortex, p->vortex, (size_t)p->n * sizeof(double), hipMemcpyHostToDevice, stream));
         }
-        std::vector<G> ax, ay;          // axes found in full arrays; alive until the copies below have landed
-        const G* hx = static_cast<const G*>(p->x_axis);
-        const G* hy = static_cast<const G*>(p->y_axis);
-        product = hx && hy;
-        if (!product) {
-            std::vector<double> dx, dy;
-            product = product_grid_axis(static_cast<const G*>(p->x_grid), p->h, p->w, 0, dx) &&
-                      product_grid_axis(static_cast<const G*>(p->y_grid), p->h, p->w, 1, dy);
-            if (product) {
-                ax.assign(dx.begin(), dx.end()); ay.assign(dy.begin(), dy.end());     // (exact: they were widened from G)
-                hx = ax.data(); hy = ay.data();
-            } else {
-                hx = static_cast<const G*>(p->x_grid); hy = static_cast<const G*>(p->y_grid);
-            }
-        }
-        const size_t nx = product ? (size_t)p->w : S, ny = product ? (size_t)p->h : S;
-        HIPCHK(x.alloc(nx)); HIPCHK(y.alloc(ny));
-        HIPCHK(hipMemcpyAsync(x, hx, nx * sizeof(G), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(y, hy, ny * sizeof(G), hipMemcpyHostToDevice, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return 0;
+        return grid.upload(p->x_axis, p->y_axis, p->x_grid, p->y_grid, p->h, p->w, stream);
     }
     int launch(const hgs_poly_params* p, void* dev_out, int out_bytes, hipStream_t stream) const {
         PolyArgs<G, void> a{};
-        a.out = dev_out; a.x = x; a.y = y; a.table = table; a.vortex = vortex;
+        a.out = dev_out; a.x = grid.x; a.y = grid.y; a.table = table; a.vortex = vortex;
         a.S = (size_t)p->h * p->w; a.W = p->w; a.deg = p->degree; a.mask_mode = p->mask_mode;
         // the scales meet the grid in ITS type (a Python float times a float32 array is a float32 product)
         a.x_scale = (double)(G)p->x_scale; a.y_scale = (double)(G)p->y_scale;
-        LCHK(launch_poly<G>(p->n, product, out_bytes, stream, a));
+        LCHK(launch_poly<G>(p->n, grid.product, out_bytes, stream, a));
         return 0;
     }
 };
@@ -209,6 +220,84 @@ template <typename G, typename W> static int poly_run_as(const hgs_poly_params* 
 template <typename W> static int poly_run(const hgs_poly_params* p, void* dev_out, int out_bytes, hipStream_t stream, W&& wrap) {
     return p->grid_bytes == 4 ? poly_run_as<float>(p, dev_out, out_bytes, stream, wrap)
                               : poly_run_as<double>(p, dev_out, out_bytes, stream, wrap);
+}
+
+// ---- grating, axicon and Gaussian-mode masks (include/hgs.h, pattern_kernels.hpp) ----------------------------------------------
+static int pattern_check(const hgs_pattern_params* p) {
+    if (!p) return fail(HGS_ERR_ARG, "null parameters");
+    if (p->h < 1 || p->w < 1) return fail(HGS_ERR_ARG, "pattern mask: h and w must be positive (got %d, %d)", p->h, p->w);
+    if (p->grid_bytes != 4 && p->grid_bytes != 8) return fail(HGS_ERR_ARG, "pattern mask: grid_bytes must be 4 or 8 (got %d)", p->grid_bytes);
+    if (p->mode < 0 || p->mode >= PAT_MODES) return fail(HGS_ERR_ARG, "pattern mask: unknown mode %d", p->mode);
+    if (p->quad && p->mode > HGS_PATTERN_BINARY) return fail(HGS_ERR_ARG, "pattern mask: only the grating modes fill quadrants (mode %d)", p->mode);
+    if (!p->quad && p->mode == HGS_PATTERN_BLAZE) return fail(HGS_ERR_ARG, "pattern mask: a plain blaze is a polynomial mask (hgs_poly_eval)");
+    for (int i = 0; i < (p->quad ? 8 : 2); ++i)
+        if (!std::isfinite(p->vec[i])) return fail(HGS_ERR_ARG, "pattern mask: the vectors must be finite");
+    if (!std::isfinite(p->shift) || !std::isfinite(p->a) || !std::isfinite(p->b) || std::isnan(p->duty))
+        return fail(HGS_ERR_ARG, "pattern mask: shift, a, b and duty must be finite");
+    if (p->mode == HGS_PATTERN_LG || p->mode == HGS_PATTERN_HG) {
+        const int lo = p->mode == HGS_PATTERN_LG ? p->p : std::min(p->n, p->m), hi = p->mode == HGS_PATTERN_LG ? p->p : std::max(p->n, p->m);
+        if (lo < 0) return fail(HGS_ERR_ARG, "pattern mask: negative order %d", lo);
+        if (hi > HGS_PATTERN_MAX_ORDER) return fail(HGS_ERR_UNSUPPORTED, "pattern mask: order %d is beyond the limit of %d", hi, HGS_PATTERN_MAX_ORDER);
+        const bool scaled = p->mode == HGS_PATTERN_HG || p->p != 0;          // (a vortex alone has no radius)
+        if (scaled && (!std::isfinite(p->radius) || p->radius == 0)) return fail(HGS_ERR_ARG, "pattern mask: the source radius must be finite and not 0");
+    }
+    const bool axes = p->x_axis && p->y_axis, grids = p->x_grid && p->y_grid;
+    if (!axes && !grids) return fail(HGS_ERR_ARG, "pattern mask: needs both axis vectors or both grid arrays");
+    return 0;
+}
+
+// NumPy's mod of a double by b > 0
+static double numpy_mod(double a, double b) {
+    double m = std::fmod(a, b);
+    if (m != 0) { if (m < 0) m += b; } else m = 0;
+    return m;
+}
+
+// the kernel's parameters from the call's: 2 pi folded into the vectors, binary's pixel-period and zero-vector rules per window
+template <typename G> static void pattern_args(const hgs_pattern_params* p, PatArgs<G, void>& a) {
+    const double two_pi = 2 * M_PI;
+    a.S = (size_t)p->h * p->w; a.W = p->w; a.H = p->h;
+    a.quad = p->quad != 0; a.round_g = p->round_grid != 0; a.dec_double = p->decision_double != 0; a.pixel_mask = 0;
+    a.l = p->l; a.p = p->p; a.n = p->n; a.m = p->m;
+    const double duty = std::min(1.0, std::max(0.0, p->duty));
+    a.shift = p->shift; a.off = two_pi * (1 - duty);
+    a.half = (p->a - p->b) / 2; a.base = p->b;
+    a.kx = p->vec[0]; a.ky = p->vec[1];
+    a.s = p->mode == HGS_PATTERN_LG && p->p != 0 ? 16.0 / p->radius / p->radius : p->mode == HGS_PATTERN_HG ? 4.0 / p->radius : 0.0;
+    for (int i = 0; i < 4; ++i) {
+        const int from = a.quad ? i : 0;
+        double vx = p->vec[2 * from], vy = p->vec[2 * from + 1];
+        PatSet& g = a.set[i];
+        g.a = p->a; g.b = p->b;
+        if (p->mode == HGS_PATTERN_BINARY) {
+            if (std::fabs(vx) > 1 || std::fabs(vy) > 1) {               // a period in pixels
+                a.pixel_mask |= 1 << i;
+                vx = vx == 0 ? 0.0 : 1.0 / vx;
+                vy = vy == 0 ? 0.0 : 1.0 / vy;
+            }
+            if (vx == 0 && vy == 0) {                                   // no grating: one level everywhere
+                const bool high = p->shift != 0 && numpy_mod(p->shift, two_pi) > two_pi * duty;
+                g.a = g.b = high ? p->a : p->b;
+            }
+        }
+        g.kx = two_pi * vx; g.ky = two_pi * vy;
+    }
+}
+
+// checked parameters -> dev_out ([h][w] of out_bytes-sized reals, aligned to out_bytes); wrap as in poly_run; complete on return
+template <typename G, typename W> static int pattern_run_as(const hgs_pattern_params* p, void* dev_out, int out_bytes, hipStream_t stream, W&& wrap) {
+    GridDevice<G> grid;
+    if (int e = grid.upload(p->x_axis, p->y_axis, p->x_grid, p->y_grid, p->h, p->w, stream)) return e;
+    PatArgs<G, void> a{};
+    pattern_args<G>(p, a);
+    a.out = dev_out; a.x = grid.x; a.y = grid.y;
+    if (int e = wrap([&]() -> int { LCHK(launch_pattern<G>(p->mode, grid.product, out_bytes, stream, a)); return 0; })) return e;
+    HIPCHK(hipStreamSynchronize(stream));        // (the buffers of grid go with this scope)
+    return 0;
+}
+template <typename W> static int pattern_run(const hgs_pattern_params* p, void* dev_out, int out_bytes, hipStream_t stream, W&& wrap) {
+    return p->grid_bytes == 4 ? pattern_run_as<float>(p, dev_out, out_bytes, stream, wrap)
+                              : pattern_run_as<double>(p, dev_out, out_bytes, stream, wrap);
 }
 
 struct EngineBase {
@@ -246,6 +335,7 @@ struct EngineBase {
     virtual int remove_vortices(int32_t* n_removed) = 0;
     virtual int get_display(const hgs_display_params* p, void* dst, size_t nbytes, bool dst_device) = 0;
     virtual int set_array_poly(int which, const hgs_poly_params* p) = 0;
+    virtual int set_array_pattern(int which, const hgs_pattern_params* p) = 0;
 };
 
 template <typename R> struct Engine : EngineBase {
@@ -1470,18 +1560,12 @@ template <typename R> struct Engine : EngineBase {
         return d2h(dst, disp_out, all, dst_device);
     }
 
-    // hgs_set_array_poly: one polynomial mask rastered into the kernel, the phase or the display correction, on the device
-    int set_array_poly(int which, const hgs_poly_params* p) override {
-        RoctxRange range(opt_roctx, "hgs_set_array_poly");
-        if (which != HGS_PROP_KERNEL && which != HGS_PHASE && which != HGS_DISPLAY_CORRECTION)
-            return fail(HGS_ERR_ARG, "hgs_set_array_poly fills HGS_PROP_KERNEL, HGS_PHASE or HGS_DISPLAY_CORRECTION (got selector %d)", which);
-        if (int e_ = poly_check(p)) return e_;
-        if (p->n != 1) return fail(HGS_ERR_ARG, "hgs_set_array_poly: one mask expected (n = %d)", p->n);
-        if (p->h != cfg.slm_h || p->w != cfg.slm_w)
-            return fail(HGS_ERR_ARG, "hgs_set_array_poly: mask of shape (%d, %d) is not of the SLM shape (%d, %d)", p->h, p->w, cfg.slm_h, cfg.slm_w);
-        auto run = [&](void* dst, int out_bytes) -> int {
-            return poly_run(p, dst, out_bytes, stream, [&](auto&& launch) -> int { return timed(HGS_K_ELEMENTWISE, launch); });
-        };
+    // one SLM-sized mask rastered into the kernel, the phase or the display correction, on the device: run(dst, out_bytes)
+    // launches and completes it
+    static bool raster_target(int which) { return which == HGS_PROP_KERNEL || which == HGS_PHASE || which == HGS_DISPLAY_CORRECTION; }
+    template <typename Run> int raster_into(const char* fn, int which, int h, int w, Run&& run) {
+        if (h != cfg.slm_h || w != cfg.slm_w)
+            return fail(HGS_ERR_ARG, "%s: mask of shape (%d, %d) is not of the SLM shape (%d, %d)", fn, h, w, cfg.slm_h, cfg.slm_w);
         if (which == HGS_DISPLAY_CORRECTION) {               // not a nearfield input: the loop never sees it
             HIPCHK(disp_corr.ensure(S));
             has_disp_corr = false;
@@ -1502,6 +1586,29 @@ template <typename R> struct Engine : EngineBase {
         }
         state.nearfield_input_changed();
         return 0;
+    }
+
+    // hgs_set_array_poly: one polynomial mask
+    int set_array_poly(int which, const hgs_poly_params* p) override {
+        RoctxRange range(opt_roctx, "hgs_set_array_poly");
+        if (!raster_target(which))
+            return fail(HGS_ERR_ARG, "hgs_set_array_poly fills HGS_PROP_KERNEL, HGS_PHASE or HGS_DISPLAY_CORRECTION (got selector %d)", which);
+        if (int e_ = poly_check(p)) return e_;
+        if (p->n != 1) return fail(HGS_ERR_ARG, "hgs_set_array_poly: one mask expected (n = %d)", p->n);
+        return raster_into("hgs_set_array_poly", which, p->h, p->w, [&](void* dst, int out_bytes) -> int {
+            return poly_run(p, dst, out_bytes, stream, [&](auto&& launch) -> int { return timed(HGS_K_ELEMENTWISE, launch); });
+        });
+    }
+
+    // hgs_set_array_pattern: one grating, axicon or Gaussian-mode mask
+    int set_array_pattern(int which, const hgs_pattern_params* p) override {
+        RoctxRange range(opt_roctx, "hgs_set_array_pattern");
+        if (!raster_target(which))
+            return fail(HGS_ERR_ARG, "hgs_set_array_pattern fills HGS_PROP_KERNEL, HGS_PHASE or HGS_DISPLAY_CORRECTION (got selector %d)", which);
+        if (int e_ = pattern_check(p)) return e_;
+        return raster_into("hgs_set_array_pattern", which, p->h, p->w, [&](void* dst, int out_bytes) -> int {
+            return pattern_run(p, dst, out_bytes, stream, [&](auto&& launch) -> int { return timed(HGS_K_ELEMENTWISE, launch); });
+        });
     }
 
     int mp_info(MpInfo* o) override {
@@ -2435,6 +2542,31 @@ int hgs_poly_eval(const hgs_poly_params* p, void* out, size_t nbytes, int out_is
     if (tmp.alloc(all) != hipSuccess) return hgs::fail(HGS_ERR_DEVICE, "hgs_poly_eval: no device memory for %zu bytes", all);
     if (int r = hgs::poly_run(p, tmp.get(), out_bytes, nullptr, plain)) return r;
     if (hipMemcpy(out, tmp.get(), all, hipMemcpyDeviceToHost) != hipSuccess) return hgs::fail(HGS_ERR_DEVICE, "hgs_poly_eval: device to host copy failed");
+    return 0;
+}
+
+int hgs_pattern_dispatch_read(char* buf, size_t nbytes, size_t* needed) { return dispatch_text_out(hgs::g_poly_log, buf, nbytes, needed); }
+
+int hgs_set_array_pattern(hgs_engine* e, int which, const hgs_pattern_params* p) { ENG(e) return e->impl->set_array_pattern(which, p); }
+
+int hgs_pattern_eval(const hgs_pattern_params* p, void* out, size_t nbytes, int out_is_device) {
+    if (int r = hgs::pattern_check(p)) return r;
+    if (!out) return hgs::fail(HGS_ERR_ARG, "null destination pointer");
+    const int out_bytes = p->out_bytes ? p->out_bytes : p->grid_bytes;
+    if (out_bytes != 4 && out_bytes != 8) return hgs::fail(HGS_ERR_ARG, "hgs_pattern_eval: out_bytes must be 0, 4 or 8 (got %d)", p->out_bytes);
+    const size_t all = (size_t)p->h * p->w * out_bytes;
+    if (nbytes != all)
+        return hgs::fail(HGS_ERR_ARG, "hgs_pattern_eval: bad size %zu (%zu expected: %d x %d %d-byte reals)", nbytes, all, p->h, p->w, out_bytes);
+    if (out_is_device && ((uintptr_t)out % (uintptr_t)out_bytes))
+        return hgs::fail(HGS_ERR_ARG, "hgs_pattern_eval: the device buffer is not aligned to its %d-byte elements", out_bytes);
+    hgs::DeviceGuard guard_(p->device, &hgs::g_poly_log);
+    if (!guard_.ok) return hgs::fail(HGS_ERR_DEVICE, "hipSetDevice(%d) failed", p->device);
+    auto plain = [](auto&& launch) -> int { return launch(); };
+    if (out_is_device) return hgs::pattern_run(p, out, out_bytes, nullptr, plain);
+    hgs::DevBuf<char> tmp;
+    if (tmp.alloc(all) != hipSuccess) return hgs::fail(HGS_ERR_DEVICE, "hgs_pattern_eval: no device memory for %zu bytes", all);
+    if (int r = hgs::pattern_run(p, tmp.get(), out_bytes, nullptr, plain)) return r;
+    if (hipMemcpy(out, tmp.get(), all, hipMemcpyDeviceToHost) != hipSuccess) return hgs::fail(HGS_ERR_DEVICE, "hgs_pattern_eval: device to host copy failed");
     return 0;
 }
 

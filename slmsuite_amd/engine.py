@@ -227,15 +227,17 @@ class Engine:
         return out
 
     def set_array_poly(self, which, mask):
-        """hgs_set_array_poly: a ``toolbox.phase.PolynomialMask`` (one mask of ``slm_shape``) rastered on the device into
-        ``PROP_KERNEL``, ``PHASE`` or ``DISPLAY_CORRECTION``; nothing SLM-sized exists on the host."""
+        """hgs_set_array_poly / hgs_set_array_pattern: a ``toolbox.phase.PolynomialMask`` or ``PatternMask`` (one mask of
+        ``slm_shape``) rastered on the device into ``PROP_KERNEL``, ``PHASE`` or ``DISPLAY_CORRECTION``; nothing SLM-sized
+        exists on the host."""
         prm, keep = mask.params(device=self.device)
-        L.check(self.lib.hgs_set_array_poly(self._h, int(which), C.byref(prm)))
+        fill = self.lib.hgs_set_array_pattern if isinstance(prm, L.hgs_pattern_params) else self.lib.hgs_set_array_poly
+        L.check(fill(self._h, int(which), C.byref(prm)))
         del keep
 
     def set_display_correction(self, arr):
         """HGS_DISPLAY_CORRECTION: the wavefront correction ``get_display`` adds (``slm.source["phase"]``), ``slm_shape``,
-        held as float64 whatever the engine's precision; ``None`` clears it.  A ``toolbox.phase.PolynomialMask`` is formed
+        held as float64 whatever the engine's precision; ``None`` clears it.  A ``toolbox.phase`` mask descriptor is formed
         on the device (``set_array_poly``)."""
         self._display_fp = self._NOT_SENT
         if arr is None:
