@@ -397,7 +397,8 @@ int hgs_sync(hgs_engine* e);
  * HGS_TILE2_BLOCKS / HGS_ROW_PREF_BLOCKS, and the A/B switches HGS_ROW_XCD, HGS_COL_XMAP, HGS_ROW_SHIFT, HGS_ROW_SHIFT64, HGS_ROW_PREF,
  * HGS_ROW_PREF_BATCH, HGS_TILE_RULE, HGS_MRAF_SPLIT, HGS_MRAF_SPLIT64, HGS_GH2_MASK, HGS_TILE_LIST, HGS_TILE_SHIFT16, HGS_TILE_NR4,
  * HGS_TILE2, HGS_TILE2_MIN_BATCH, HGS_TILE2_PHASE2, HGS_KEEP_G, HGS_FUSED_SHIFT, HGS_MONO_TAB, HGS_MRAF_PRESUM, HGS_PRESUM_ROWS,
- * HGS_PRESUM_BLOCKS, HGS_EMPTY_COL_LOADS, HGS_EMPTY_COL_INVERSE, HGS_EMPTY_COL_FORWARD -- all default to the tuned path;
+ * HGS_PRESUM_BLOCKS, HGS_EMPTY_COL_LOADS, HGS_EMPTY_COL_INVERSE, HGS_EMPTY_COL_FORWARD,
+ * HGS_EMPTY_COL_PREZERO -- all default to the tuned path;
  * HGS_TRACE_INIT=1 prints where hgs_create spends its time).
  *   HGS_KEEP_G (default 1): the last row launch of a float32 hgs_iterate call leaves G of the next body behind, and the next
  *   call -- or hgs_nearfield2farfield -- on an unchanged phase starts from it.  That G is the loop's own un-rounded phasor
@@ -419,6 +420,13 @@ int hgs_sync(hgs_engine* e);
  *   barrier: it only stores its zeros into H.  Every column of H is still written.  It rests on the inverse skip: with
  *   HGS_OPT_EMPTY_COL_INVERSE = 0 it does nothing.  hgs_dispatch_read marks the launches that skip with `zero_fwd`.
  *   HGS_PHASE and HGS_WEIGHTS are the same bit for bit; 0 loads and transforms every column (the tests' A/B reference).
+ * HGS_OPT_EMPTY_COL_PREZERO (default 1; HGS_EMPTY_COL_PREZERO in the environment): where HGS_OPT_EMPTY_COL_FORWARD acts and the
+ *   body is nothing but that column launch and its row launch, the zeros of the empty columns are written by the ROW launch that
+ *   closes the body before: it stores zero instead of G in the columns the scan found empty (`zero_mask` in hgs_dispatch_read
+ *   -- the same stores, one select each), and the column launch walks from one non-empty half tile to the next without touching
+ *   the empty ones (`prezero`).  Inside one hgs_iterate call only: the first body of a call runs the plain form, the last row
+ *   launch of a call leaves G of every column as before, so calls of a single body gain nothing.  HGS_PHASE and HGS_WEIGHTS are
+ *   the same bit for bit; 0 has every column launch store its zeros itself (the tests' A/B reference).
  * HGS_OPT_ROCTX (default 0): roctx ranges (hgs_iterate, hgs_nearfield2farfield, hgs_farfield_constraint,
  *   hgs_farfield2nearfield) for rocprofv3 --marker-trace; the roctx library is dlopen'ed on first use.
  * HGS_OPT_KEEP_PREV_PHASE (default 0): a fused hgs_iterate / hgs_iterate_stats call of ONE iteration that rewrites the
@@ -430,7 +438,7 @@ int hgs_sync(hgs_engine* e);
 enum { HGS_OPT_SPARSE_COLUMNS = 1, HGS_OPT_FORCE_STEPWISE = 2, HGS_OPT_TILE_KERNEL = 3, HGS_OPT_SEPARABLE = 4,
        HGS_OPT_SEPARABLE_MIN_SPOTS = 5, HGS_OPT_ROCTX = 6, HGS_OPT_RUN_KERNELS = 7, HGS_OPT_KEEP_PREV_PHASE = 8,
        HGS_OPT_EMPTY_COL_LOADS = 9, HGS_OPT_SEP_WORKGROUPS = 10,
-       HGS_OPT_EMPTY_COL_INVERSE = 11, HGS_OPT_EMPTY_COL_FORWARD = 12 };
+       HGS_OPT_EMPTY_COL_INVERSE = 11, HGS_OPT_EMPTY_COL_FORWARD = 12, HGS_OPT_EMPTY_COL_PREZERO = 13 };
 int hgs_set_option(hgs_engine* e, int option, int value);
 
 /* Timing support for bench.py: per-kernel HIP-event timing on the engine stream. */
@@ -450,7 +458,7 @@ int hgs_iterate_timed(hgs_engine* e, hgs_step* step, int n_iter, double* ms);
  * per (instance, run-time flags):
  *     "col_tile_kernel<R=float,N=4096,PHASE=0,NR=6,STATS=false,EXTRAS=false,RULE=1,LISTED=0> xmap\t50\n"
  * (family, its template arguments by name -- the ones rocprofv3 prints positionally --, flags list / load_mask /
- * store_mask / xmap / batch / stats / nf_out, launch count).  Families: row_kernel, col_kernel, col_fused_kernel,
+ * store_mask / xmap / batch / stats / nf_out / ..., launch count).  Families: row_kernel, col_kernel, col_fused_kernel,
  * col_tile_kernel, bluestein_lines, c_n2f_run, c_f2n_run, c_n2f_partial, c_f2n, cgemm_streamk, cg_seed_kernel, cg_adam_kernel,
  * vortex_find_kernel, vortex_remove_kernel, phase_display_kernel, poly_kernel, pattern_kernel
  * (the small element-wise / reduction helpers are not recorded).  The tests assert it next to the numbers: neighbouring variants often agree to

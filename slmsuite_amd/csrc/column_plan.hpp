@@ -44,6 +44,9 @@ struct Tuning {
                                 // of those columns as well (the flags still go with the launch)
     int empty_col_forward = 1;  // HGS_EMPTY_COL_FORWARD=0 / HGS_OPT_EMPTY_COL_FORWARD: ... and, where the inverse is skipped, loads and
                                 // transforms them forward although nothing reads the result (acts only with empty_col_inverse)
+    int empty_col_prezero = 1;  // HGS_EMPTY_COL_PREZERO=0 / HGS_OPT_EMPTY_COL_PREZERO: ... and, where the forward transform is skipped, every
+                                // body of a call stores the zeros of the empty columns itself instead of finding them left by the row
+                                // launch before it (acts only with empty_col_forward; prezero_ok below)
     int sparse = 1;             // HGS_OPT_SPARSE_COLUMNS
     int tile = 1;               // HGS_OPT_TILE_KERNEL (0 forces the per-column kernel at every size: the tests' A/B reference)
 };
@@ -376,6 +379,22 @@ inline ColumnPlan plan_column_pass(const PassFacts& f) {
     cp.need_dpartial = m.presum || m.presum_col;
     cp.need_nog_dev = cp.nog;
     return cp;
+}
+
+// The row launch that closes body i may store the zero H of the empty columns instead of G (RowArgs::zero_mask), and the main
+// launch of body i + 1 then walks past empty half tiles (ColArgs::h_prezeroed), where the plan of body i + 1 says all of this:
+// the half-width kernel with the scan's flags (a current scan, no weight written behind it, no column list, at most five
+// slots: column_launch), the instance that reads them (PHASE 0, 4096 rows), every empty-column switch on, and nothing else in
+// the body that reads or writes gh -- no second pass, Nogrette sum, pre-pass or in-pass statistics.  Pure, like the plan: the
+// engine asks it of the NEXT body's plan ahead of the closing row launch and of the body's own plan ahead of its column launch.
+inline bool prezero_ok(const ColumnPlan& cp, const PassFacts& f) {
+    const Tuning& t = f.tun;
+    const ColLaunch& l = cp.main;
+    if (f.elem != 4 || f.Ph != 4096) return false;
+    if (l.family != ColFamily::tile2 || !l.col_flags || l.phase_mode != 0) return false;
+    if (!t.empty_col_inverse || !t.empty_col_forward || !t.empty_col_prezero) return false;
+    if (cp.second_pass || cp.nog || cp.presum || cp.presum_col || cp.dilated_forward || cp.noise_inverse_grid || l.stats || f.stat_groups) return false;
+    return cp.join == RowJoin::none;
 }
 
 // spot feedback on a sparse target (Engine::iterate_spot_sparse): the fused launch over the spot columns, weight update off

@@ -25,6 +25,8 @@ enum : unsigned {
     DF_ZERO_INV = 512u,  // col_tile2_kernel with the column flags: empty columns skip rule block and inverse (ColArgs::zero_inv)
     DF_ZERO_FWD = 1024u, // ... and are neither loaded nor transformed forward; an empty half tile only stores zeros (ColArgs::zero_fwd)
     DF_QUAD = 2048u,     // pattern_kernel: four windows, each with its own grating (PatArgs::quad)
+    DF_PREZERO = 4096u,  // col_tile2_kernel with zero_fwd: H of the empty columns is in place already, empty half tiles are walked past (ColArgs::h_prezeroed)
+    DF_ZERO_MASK = 8192u, // row kernel: stores that zero H instead of G in the columns the scan found empty (RowArgs::zero_mask)
 };
 
 struct DispatchSite {
@@ -59,6 +61,7 @@ inline void dispatch_note(const DispatchSite* s, unsigned flags = 0) {
 // kernel families (template parameter names in declaration order, the element type first)
 #define HGS_FAMILY(tag, kname, plist) struct tag { static constexpr const char* name = kname; static constexpr const char* params = plist; }
 HGS_FAMILY(KRow, "row_kernel", "R,N,MODE,NS,PREF,SPLIT");
+HGS_FAMILY(KRowZ, "row_kernel", "R,N,MODE,NS,PREF,SPLIT");   // row_zmask_kernel: the same instance with RowArgs::zero_mask honoured (flag zero_mask)
 HGS_FAMILY(KCol, "col_kernel", "R,N,MODE");
 HGS_FAMILY(KFused, "col_fused_kernel", "R,N,PHASE,STATS,RULE,NRS");
 HGS_FAMILY(KTile, "col_tile_kernel", "R,N,PHASE,NR,STATS,EXTRAS,RULE,LISTED");

@@ -62,7 +62,7 @@ thread_local DispatchLog* g_dispatch = nullptr;
 // one line per (kernel instance, run-time flags): "family<P0=v0,...> flag ...\tcount\n".  The argument values come from
 // __PRETTY_FUNCTION__ of dispatch_site<Fam, R, V...>: "... [Fam = hgs::KTile, R = float, V = <4096, 1, 6, false, false, 1, 0>]"
 std::string DispatchLog::text() const {
-    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags", "sk_cap", "zero_inv", "zero_fwd", "quad"};
+    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags", "sk_cap", "zero_inv", "zero_fwd", "quad", "prezero", "zero_mask"};
     std::string out;
     for (const Ent& e : v) {
         std::vector<std::string> vals;
@@ -511,6 +511,7 @@ template <typename R> struct Engine : EngineBase {
         t.empty_col_loads = env_int("HGS_EMPTY_COL_LOADS", 1);
         t.empty_col_inverse = env_int("HGS_EMPTY_COL_INVERSE", 1);
         t.empty_col_forward = env_int("HGS_EMPTY_COL_FORWARD", 1);
+        t.empty_col_prezero = env_int("HGS_EMPTY_COL_PREZERO", 1);
         return t;
     }
 
@@ -1206,10 +1207,14 @@ template <typename R> struct Engine : EngineBase {
     // load / store: 0 = every column, 1 = active columns, 2 = active columns dilated by the spot windows
     // mode: row_kernel MODE (3 = MODE 2 that also writes the phase; float32 only)
     // cp: the column pass this launch closes (the partials it folds, the join of a single-pass MRAF body), or null
-    int run_row(int mode, bool finalize, int load_sparse = 0, int store_sparse = 0, const ColumnPlan* cp = nullptr) {
+    // zero_par: -1, or RowArgs::zero_par of a MODE 2 launch inside a call that stores the zero H of the columns the scan found
+    // empty instead of their G (the next body's column launch walks past them: ColArgs::h_prezeroed)
+    int run_row(int mode, bool finalize, int load_sparse = 0, int store_sparse = 0, const ColumnPlan* cp = nullptr, int zero_par = -1) {
         state.row_launch_begins();
-        int r_ = run_row_impl(mode, finalize, load_sparse, store_sparse, cp);
-        if (r_ == 0) state.row_stored_g(mode, store_sparse);      // gh holds G of the columns this launch stored
+        int r_ = run_row_impl(mode, finalize, load_sparse, store_sparse, cp, zero_par);
+        // gh holds G of the columns this launch stored -- of none that a later call may count on where it stored zeros instead
+        // (an error return in mid-loop must not leave a G behind that is none)
+        if (r_ == 0) state.row_stored_g(mode, zero_par >= 0 ? -1 : store_sparse);
         return r_;
     }
     // (fused loops only; p = the plan of the call's first iteration)
@@ -1223,11 +1228,22 @@ template <typename R> struct Engine : EngineBase {
         return 0;
     }
     bool gh_holds(int need) const { return state.gh_holds(need, tun.keep_g != 0); }
-    int run_row_impl(int mode, bool finalize, int load_sparse, int store_sparse, const ColumnPlan* cp) {
+    int run_row_impl(int mode, bool finalize, int load_sparse, int store_sparse, const ColumnPlan* cp, int zero_par = -1) {
         return timed(HGS_K_ROW, [&]() -> int {
             RowArgs<R> a = row_args(finalize, cp ? cp->wpartial_n : 0);
             a.load_mask = load_sparse == 1 ? active.mask.get() : load_sparse == 2 ? dilated.mask.get() : nullptr;
             a.store_mask = store_sparse == 1 ? active.mask.get() : store_sparse == 2 ? dilated.mask.get() : nullptr;
+            if (zero_par >= 0) {
+                if (sizeof(R) != 4 || mode != 2 || a.load_mask || a.store_mask || (cp && cp->join != RowJoin::none))
+                    return fail(HGS_ERR_STATE, "zero-masked row launch outside a plain fp32 MODE 2 launch");
+                // bit 0 of the scan, per lane and register slot.  The mask of the active-column list IS that: it is built
+                // from "any bit of the scan byte" (ColList::build with 0xff), the scan sets bit 1 (a finite non-zero target)
+                // and bit 2 (a NaN target) only where it sets bit 0 (either is a target that is not zero), and the rounding
+                // to whole tiles ORs bit 0 itself into the bytes of a tile -- so a byte is non-zero exactly when bit 0 is set.
+                // Built once per scan, next to the other masks (refresh_sparse).
+                a.zero_mask = active.mask.get();
+                a.zero_par = zero_par;
+            }
             // one extra (row-less) block folds the weight-norm partials when asked to
             // dense fp32 launches between iterations at 4096: workgroups walk several rows, next row prefetched into LDS
             int blocks = row_blocks;
@@ -1895,7 +1911,8 @@ template <typename R> struct Engine : EngineBase {
         }
     }
     // one launch of the column pass; then_scale: wscale = 1/||w'|| from its partials right after it (reduce_to_scale)
-    int launch_column(const ColLaunch& l, const CParams<R>& cprm, bool then_scale = false) {
+    // prezeroed: the row launch immediately before, in this call, stored the zeros of the empty columns (prezero_ok)
+    int launch_column(const ColLaunch& l, const CParams<R>& cprm, bool then_scale = false, bool prezeroed = false) {
         return timed(HGS_K_COL_FUSED, [&]() -> int {
             ColArgs<R> a = col_args();
             a.cp = cprm;
@@ -1920,6 +1937,7 @@ template <typename R> struct Engine : EngineBase {
                 a.col_flags = col_active;
                 a.zero_inv = tun.empty_col_inverse ? 1 : 0;
                 a.zero_fwd = (a.zero_inv && tun.empty_col_forward) ? 1 : 0;      // (the forward skip rests on the inverse skip)
+                a.h_prezeroed = (a.zero_fwd && prezeroed) ? 1 : 0;
             }
             a.few_active = l.few_active ? 1 : 0;
             if (l.family == ColFamily::tile_split || l.family == ColFamily::tile_split_stats) { a.gh2 = gh2; a.gh2_sparse = l.gh2_sparse ? 1 : 0; }
@@ -2065,6 +2083,9 @@ template <typename R> struct Engine : EngineBase {
         if (int e = keep_prev_phase(p, n)) return e;
         // (the previous call may have left G of these columns behind: gh_state, row_kernel MODE 3)
         if (!gh_holds(sp ? store_sparse : 0)) { if (int e = run_row(0, false, 0, sp ? store_sparse : 0)) return e; }
+        // the row launch that closed the body before, in THIS call, stored zeros in the empty columns of gh (never kept across
+        // calls: the last launch of a call leaves G of every column)
+        bool gh_prezeroed = false;
         for (int i = 0; i < n; ++i) {
             state.column_pass_begins();
             if (p.use_fixed || p.store_phase) { if (int e = need_pff()) return e; }
@@ -2077,12 +2098,18 @@ template <typename R> struct Engine : EngineBase {
             if (scans.noise || scans.signal || scans.flags) f = pass_facts(st, p, sp);
             ColumnPlan cp = plan_column_pass(f);
             if (int e = acquire(cp, f)) return e;
+            // (flags cannot change inside a call; a body that scans them again takes the plain form, which writes the same zeros)
+            if (scans.flags) gh_prezeroed = false;
+            // the row launch before decided on the plan of THIS body (same pure function, same facts): where it stored zeros,
+            // this launch must be the one that counts on them -- any other would read them as G
+            if (gh_prezeroed && !prezero_ok(cp, f)) return fail(HGS_ERR_STATE, "zero-masked G ahead of a column pass that reads every column");
             // execute
             const CParams<R> cprm = cparams(st, p);
             if (cp.dilated_forward) { if (int e = launch_dilated_forward()) return e; }
             if (int e = launch_prepass(cp, cprm)) return e;
             if (cp.nog) { if (int e = launch_column(cp.nog_pass, cprm)) return e; }
-            if (int e = launch_column(cp.main, cprm, cp.scale_after_main)) return e;
+            if (int e = launch_column(cp.main, cprm, cp.scale_after_main, gh_prezeroed)) return e;
+            gh_prezeroed = false;
             if (cp.second_pass) { if (int e = launch_column(cp.second, cprm)) return e; }
             if (int e = launch_noise_inverse(cp)) return e;
             if (stat_ctx) { if (int e = fused_stats_finish(i, cp)) return e; }
@@ -2095,8 +2122,20 @@ template <typename R> struct Engine : EngineBase {
             // the row launch that closes the iteration: on the sparse path it reads the active columns and writes those the
             // next column launches read; the last one of the call extracts the phase (cp.last_mode)
             const bool last = i + 1 == n;
-            if (int e = run_row(last ? cp.last_mode : 2, cp.finalize, sp ? 1 : 0, (last && cp.last_mode == 3) ? 0 : (sp ? store_sparse : 0), &cp))
+            // HGS_OPT_EMPTY_COL_PREZERO: where the NEXT body's main launch is the half-width kernel with the scan's flags and
+            // nothing else of that body touches gh (prezero_ok on its plan -- the facts are those it will form itself: nothing
+            // between here and there changes them, and no scan runs for such a body), this launch stores the zero H of the
+            // empty columns instead of their G, which that launch would not read.  Never the last launch of a call.
+            int zero_par = -1;
+            if (!last && sizeof(R) == 4 && cp.join == RowJoin::none && !sp) {
+                const PassFacts fn = pass_facts(st, pn, sp);
+                const ColumnPlan cpn = plan_column_pass(fn);
+                const Scans sn = scans_needed(fn);
+                if (prezero_ok(cpn, fn) && !sn.noise && !sn.signal && !sn.flags) zero_par = (g.r0 - cpn.main.shift) & 1;
+            }
+            if (int e = run_row(last ? cp.last_mode : 2, cp.finalize, sp ? 1 : 0, (last && cp.last_mode == 3) ? 0 : (sp ? store_sparse : 0), &cp, zero_par))
                 return e;
+            gh_prezeroed = zero_par >= 0;
             p = pn;
         }
         return 0;
@@ -2332,6 +2371,7 @@ template <typename R> struct Engine : EngineBase {
             case HGS_OPT_EMPTY_COL_LOADS: tun.empty_col_loads = value ? 1 : 0; return 0;
             case HGS_OPT_EMPTY_COL_INVERSE: tun.empty_col_inverse = value ? 1 : 0; return 0;
             case HGS_OPT_EMPTY_COL_FORWARD: tun.empty_col_forward = value ? 1 : 0; return 0;
+            case HGS_OPT_EMPTY_COL_PREZERO: tun.empty_col_prezero = value ? 1 : 0; return 0;
             case HGS_OPT_KEEP_PREV_PHASE: opt_prev_phase = value ? 1 : 0; if (!value) state.prev_phase_dropped(); return 0;
             case HGS_OPT_ROCTX:
                 if (value && !g_roctx.load()) return fail(HGS_ERR_UNSUPPORTED, "no roctx library (librocprofiler-sdk-roctx / libroctx64) found");

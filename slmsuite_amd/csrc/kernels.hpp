@@ -550,6 +550,13 @@ template <typename R> struct RowArgs {
                          // the phase (_farfield2nearfield(extract=False), MultiplaneHologram)
     const Cx<R>* gh2;    // row_kernel SPLIT: the noise-region part of an MRAF field (layout of gh); H = gh * wscale + gh2
     const unsigned short* gh2_mask;   // ... and the columns in which it exists (a NaN target in the column); nullptr = all
+    // fp32 MODE 2 only (HGS_OPT_EMPTY_COL_PREZERO): laid out like load_mask; a column whose bit is CLEAR -- bit 0 of its scan byte
+    // clear: the column launch of the next body neither reads its G nor does anything but zero its H -- is stored as that zero
+    // instead of G, so that the column launch has nothing to do there (ColArgs::h_prezeroed).  nullptr = G of every column.
+    // Never together with load_mask / store_mask or SPLIT; it does not take the prefetching form away.
+    const unsigned short* zero_mask;
+    int zero_par;        // ... the zero of row r is -0 where r + zero_par is odd, +0 elsewhere: the bits 0 * (+-scale) the column
+                         // kernel leaves in H of an empty column (the sign is its space-side lane parity, r - shift + r0)
 };
 
 // NS < 16 (one-row workgroups only): the SLM columns occupy at most NS of the 16 register slots of the space side.  The
@@ -572,13 +579,11 @@ __device__ __forceinline__ void glds16(const void* src, void* lds_dst) {
 // SPLIT (single-pass MRAF, col_tile_kernel RULE 3): the column kernel left the two parts of the constrained field apart,
 // A = the signal region with the UN-normalised new weights (gh) and B = the noise region (gh2), both already transformed
 // along the columns; the row to transform is A / ||w'|| + B (the transforms are linear, and ||w'|| is known by now).
-template <typename R, int N, int MODE, int NS = 16, bool PREF = false, bool SPLIT = false>
-// (8192-wide rows: a workgroup is 8 waves, two per SIMD -- a second resident workgroup needs four waves per SIMD,
-//  i.e. at most 128 VGPRs)
-// (the phase-extracting forms over all 16 register slots, MODE 1 / 3 with NS = 16 from 4096 columns on, and MODE 3 below
-//  that -- one launch per engine call -- are compiled for two waves per SIMD: at three / four they spilled 4 .. 48 VGPRs)
-__global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 || MODE == 3) && NS == 16 && N >= 4096 && !SPLIT) || (MODE == 3 && N < 4096)) ? 2 :
-                                             (N >= 8192 ? HGS_ROW_OCC_8192 : PREF ? 2 : HGS_ROW_OCC))) void row_kernel(RowArgs<R> a) {
+// The body of the row kernels.  ZM: the instance honours RowArgs::zero_mask (row_zmask_kernel below); every other instance
+// carries no trace of it -- compiled into all fp32 MODE 2 instances behind a pointer test, the select cost the launches that
+// never receive a mask 1 - 3 % (a dense image at 4096 columns, the 2048-wide form: NOTEBOOK.md, "H pre-zeroed by the row launch").
+template <typename R, int N, int MODE, int NS, bool PREF, bool SPLIT, bool ZM>
+__device__ __forceinline__ void row_body(const RowArgs<R>& a) {
     static_assert(NS == 16 || (RowCfg<N>::FPW == 1 && NS >= 4 && NS < 16), "row_kernel: shifted form is for one-row workgroups");
     static_assert(!PREF || (sizeof(R) == 4 && N == 4096 && MODE == 2), "row_kernel: the prefetching form is fp32, 4096 wide, MODE 2");
     static_assert(!SPLIT || (!PREF && MODE != 0 && RowCfg<N>::T >= 256), "row_kernel: the split form reads H, one-row workgroups");
@@ -689,6 +694,13 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
     if constexpr (PREF) {
         if (first < g.Sh) prefetch_row(first);      // (no wait here: the set-up below runs under the first row's flight)
     }
+    // RowArgs::zero_mask: columns whose bit is clear are stored as the zero H the next column launch would write there.  A
+    // select per stored value on the lane's own mask bits -- never a multiply: G may hold anything, the zero is exact.
+    // (fetched here, under the first row's flight in the prefetching form)
+    constexpr bool ZMASK = ZM;
+    static_assert(!ZM || (sizeof(R) == 4 && MODE == 2 && !SPLIT), "row kernels: the zero mask is for the plain fp32 MODE 2 instances");
+    unsigned zmask = 0xffffu;
+    if constexpr (ZMASK) { if (a.zero_mask != nullptr) zmask = fetch_mask(a.zero_mask); }
     HGS_T(fft.tr_n, 1);
 #pragma unroll 1
     for (int rbase = first; rbase < g.Sh; rbase += row_stride) {
@@ -780,7 +792,13 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                 static_for<0, 16>([&](auto m_) {
                     constexpr int m = m_;
                     const unsigned vo = ((smask >> m) & 1u) ? ghl : BUF_OOB;
-                    bgh.template st<Cx<R>>(v[m] * sc, vo, ghr0 + (unsigned)m * ghs);
+                    Cx<R> e = v[m] * sc;
+                    if constexpr (ZMASK) {
+                        const R zr = ((r + a.zero_par) & 1) ? (R)-0.0 : (R)0;
+                        const bool keep = ((zmask >> m) & 1u) != 0u;
+                        e = mk<R>(keep ? e.x : zr, keep ? e.y : zr);
+                    }
+                    bgh.template st<Cx<R>>(e, vo, ghr0 + (unsigned)m * ghs);
                 });
 #if HGS_TRACE
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -946,6 +964,13 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
             if (valid) {
                 const R sc = sgn * a.scale;
                 const Cx<R> omsc = om * sc;
+                // (RowArgs::zero_mask: the zero of this row, see zero_par; a scalar where the row is the wave's)
+                const R zr = (ZMASK && ((r + a.zero_par) & 1)) ? (R)-0.0 : (R)0;
+                // (the mask is made opaque per row: taken as loop-invariant, its sixteen lane conditions were hoisted into SGPR
+                //  pairs that live across the whole row loop -- 33 more spilled SGPRs in the prefetching instance, read back
+                //  lane by lane ahead of every store)
+                unsigned zm = zmask;
+                if constexpr (ZMASK) asm volatile("" : "+v"(zm));
                 // Dense fp32 launches: the sixteen 8-byte stores of a lane are store-ISSUE bound (2.7 k of the 16.3 k cycles of
                 // a row in tools/microbench/trace_row; MI355X_MICROARCH.md: 8 x dwordx4 halves such a tail).  Lanes j, j + 1
                 // (j even) own neighbouring columns of the same tile row, so they swap one value per pair of register slots
@@ -962,6 +987,11 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                             Cx<R> e0, e1;
                             if constexpr (NS < 16) { e0 = cmul(v[m], omsc); e1 = cmul(v[m + 1], omsc); }
                             else { e0 = v[m] * sc; e1 = v[m + 1] * sc; }
+                            if constexpr (ZMASK) {          // each lane masks its OWN two values, ahead of the swap
+                                const bool k0 = ((zm >> m) & 1u) != 0u, k1 = ((zm >> (m + 1)) & 1u) != 0u;
+                                e0 = mk<R>(k0 ? e0.x : zr, k0 ? e0.y : zr);
+                                e1 = mk<R>(k1 ? e1.x : zr, k1 ? e1.y : zr);
+                            }
                             const R sx = odd ? e0.x : e1.x, sy = odd ? e0.y : e1.y;       // what the neighbour stores for me
                             const R kx = odd ? e1.x : e0.x, ky = odd ? e1.y : e0.y;       // what I store myself
                             const R rx = __builtin_bit_cast(R, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, sx), 0xB1, 0xf, 0xf, true));
@@ -982,8 +1012,14 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
                 static_for<0, 16>([&](auto m_) {
                     constexpr int m = m_;
                     if ((smask >> m) & 1u) {
-                        if constexpr (NS < 16) (ghr + (size_t)m * gh_step)[gh_lane] = cmul(v[m], omsc);
-                        else (ghr + (size_t)m * gh_step)[gh_lane] = v[m] * sc;
+                        Cx<R> e;
+                        if constexpr (NS < 16) e = cmul(v[m], omsc);
+                        else e = v[m] * sc;
+                        if constexpr (ZMASK) {
+                            const bool keep = ((zm >> m) & 1u) != 0u;
+                            e = mk<R>(keep ? e.x : zr, keep ? e.y : zr);
+                        }
+                        (ghr + (size_t)m * gh_step)[gh_lane] = e;
                     }
                 });
             }
@@ -997,6 +1033,25 @@ __global__ __launch_bounds__(RowCfg<N>::WG, (sizeof(R) == 8 ? 2 : (((MODE == 1 |
 #if HGS_TRACE
     if (a.nf_out != nullptr && MODE == 2) trace_dump(a.nf_out, 512);   // the microbenchmark passes its dump buffer through nf_out
 #endif
+}
+
+// (8192-wide rows: a workgroup is 8 waves, two per SIMD -- a second resident workgroup needs four waves per SIMD,
+//  i.e. at most 128 VGPRs)
+// (the phase-extracting forms over all 16 register slots, MODE 1 / 3 with NS = 16 from 4096 columns on, and MODE 3 below
+//  that -- one launch per engine call -- are compiled for two waves per SIMD: at three / four they spilled 4 .. 48 VGPRs)
+template <typename R, int N, int MODE, int NS, bool PREF, bool SPLIT> constexpr int row_min_waves() {
+    return sizeof(R) == 8 ? 2 : (((MODE == 1 || MODE == 3) && NS == 16 && N >= 4096 && !SPLIT) || (MODE == 3 && N < 4096)) ? 2 :
+           (N >= 8192 ? HGS_ROW_OCC_8192 : PREF ? 2 : HGS_ROW_OCC);
+}
+template <typename R, int N, int MODE, int NS = 16, bool PREF = false, bool SPLIT = false>
+__global__ __launch_bounds__(RowCfg<N>::WG, (row_min_waves<R, N, MODE, NS, PREF, SPLIT>())) void row_kernel(RowArgs<R> a) {
+    row_body<R, N, MODE, NS, PREF, SPLIT, false>(a);
+}
+// ... and the instances that store zero instead of G where RowArgs::zero_mask says so (fp32, MODE 2, not the split form): the
+// same template arguments, and the dispatch record lists them as row_kernel<...> with the flag `zero_mask`
+template <typename R, int N, int MODE, int NS = 16, bool PREF = false, bool SPLIT = false>
+__global__ __launch_bounds__(RowCfg<N>::WG, (row_min_waves<R, N, MODE, NS, PREF, SPLIT>())) void row_zmask_kernel(RowArgs<R> a) {
+    row_body<R, N, MODE, NS, PREF, SPLIT, true>(a);
 }
 
 // =====================================================================================================
@@ -1059,6 +1114,9 @@ template <typename R> struct ColArgs {
                            // block and its inverse transform -- the constrained column is exactly zero, so is its inverse
     int zero_fwd;          // ... (HGS_OPT_EMPTY_COL_FORWARD, only with zero_inv) and is neither loaded nor transformed forward: nothing
                            // reads the farfield of such a column; a half tile of two empty columns only stores its zeros
+    int h_prezeroed;       // ... (HGS_OPT_EMPTY_COL_PREZERO, only with col_flags and zero_fwd) and the row launch ahead of this one has
+                           // already left those zeros in the empty columns of gh (RowArgs::zero_mask): a workgroup walks from one
+                           // non-empty half tile to the next and an empty one costs a scalar look at its flag word
     int fnr;               // col_fused_kernel: register slots the shifted SLM rows occupy (0 = the unshifted kernel, NRS = 16)
     int fshift;            // col_fused_kernel<..., NRS < 16> (float64, >= 4096 rows): circular shift of the transform input, a
                            // multiple of 16 rows (shift theorem, as in col_tile_kernel): the SLM rows occupy slots 0 .. NRS - 1
@@ -2408,7 +2466,19 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
     const int* cflag4 = (WTBUF && a.col_flags != nullptr) ? reinterpret_cast<const int*>(a.col_flags + (size_t)b * g.Pw) : nullptr;
     int fw = -1, fwn = -1;                       // scan bytes of this tile / of the group's next one (-1: every column fetched)
     const bool wt_buf = WTBUF && (NXF || cflag4 != nullptr);        // (uniform; NXF: a constant)
-    if constexpr (WTBUF) { if (cflag4 != nullptr && ct0 < ntiles) fw = uniform_load_i32(cflag4 + ct0); }
+    // a.h_prezeroed (with the flags and a.zero_fwd): the row launch before this one stored the zeros of the empty columns, so an
+    // empty half tile has nothing left to do.  The workgroup keeps its static schedule (ct0, ct_step, half) but visits only the
+    // half tiles that are not empty, in the same order -- acc_w sums the same columns as before -- and `more`, fwn, the rows
+    // requested ahead and the weight / target chain refer to the NEXT NON-EMPTY half tile (ctn).  Finding it is a scalar walk
+    // over flag words, the same in all four waves, outside every barrier region; skip_ht is then never true in the loop.
+    bool prez = false;
+    if constexpr (WTBUF && PHASE == 0) prez = cflag4 != nullptr && a.zero_fwd != 0 && a.h_prezeroed != 0;
+    auto flag_word = [&](int i) { return uniform_load_i32(cflag4 + i); };
+    int ct = ct0;
+    if constexpr (WTBUF) {
+        if (prez) ct = tile2_next_nonempty(flag_word, ct0, ct_step, ntiles, half, &fw);
+        else if (cflag4 != nullptr && ct0 < ntiles) fw = uniform_load_i32(cflag4 + ct0);
+    }
     // PARK: the rows of the workgroup's NEXT half tile are requested BEFORE the stores of the current one (vmcnt retires in order:
     // behind the stores, the wait for the new rows also waited for the stores to be acknowledged -- tools/microbench/trace_tile2:
     // 6.3 k cycles per half tile); they travel in the registers the finished tile has just freed
@@ -2422,7 +2492,7 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
     //  rows, which the other two workgroups of the CU cover -- costs 20 registers that stay live across the rolled column loop:
     //  17 / 31 spilled at five / six slots.)
 #pragma unroll 1
-    for (int ct = ct0; ct < ntiles; ct += ct_step) {
+    while (ct < ntiles) {
         Cx<R>* gh = a.gh + (size_t)b * g.Sh * g.Pw + (size_t)ct * g.Sh * 4 + 2 * half;
         HGS_T(fft.tr_n, 1);
         // The half tile's rows through a buffer resource (rows outside the SLM are outside the resource: they read as zero), all
@@ -2453,8 +2523,13 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 tq[TBUF ? m : 0] = bt.template ld<float4>((unsigned)(r_lane + m * T) * 4u * (unsigned)sizeof(Cx<R>), 0u);   // (negative rows wrap out of range)
         }
         const int col0 = ct * 4 + 2 * half;
-        const bool more = ct + ct_step < ntiles;
-        if constexpr (WTBUF) { if (cflag4 != nullptr && more) fwn = uniform_load_i32(cflag4 + ct + ct_step); }
+        // the workgroup's next half tile: ct + ct_step, or with a.h_prezeroed the next one that is not empty (>= ntiles: none)
+        int ctn = ct + ct_step;
+        if constexpr (WTBUF) {
+            if (prez) ctn = tile2_next_nonempty(flag_word, ctn, ct_step, ntiles, half, &fwn);
+            else if (cflag4 != nullptr && ctn < ntiles) fwn = uniform_load_i32(cflag4 + ctn);
+        }
+        const bool more = ctn < ntiles;
         float4 outq[PARK ? NR : 1];
         if (!skip_ht) {
 #pragma unroll
@@ -2577,12 +2652,12 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
             {   // weights / target of the next column (or of the first column of this group's next half tile)
                 if (wt_buf) {
                     // (straight-line: no next half tile = an empty resource on this column)
-                    const int ncol = c == 0 ? col0 + 1 : more ? (ct + ct_step) * 4 + 2 * half : col0;
+                    const int ncol = c == 0 ? col0 + 1 : more ? ctn * 4 + 2 * half : col0;
                     const bool nact = c == 0 ? tile2_col_active(fw, half, 1) : more && tile2_col_active(fwn, half, 0);
                     issue_wt_loads_buf<R, T>(wbase + (size_t)ncol * g.Ph, tbase + (size_t)ncol * g.Ph, nact ? col_bytes : 0u,
                                              do_upd, j, wr, tr);
                 } else {
-                    const int ncol = c == 0 ? col0 + 1 : (ct + ct_step) * 4 + 2 * half;
+                    const int ncol = c == 0 ? col0 + 1 : ctn * 4 + 2 * half;
                     if (c == 0 || more)
                         issue_wt_loads<R, T>(wbase + (size_t)ncol * g.Ph, tbase + (size_t)ncol * g.Ph, do_upd, j, wr, tr);
                 }
@@ -2636,7 +2711,7 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
             // `first` or from the half tile before it -- here that is this one.  ONE request, for the first column of the
             // workgroup's next half tile (an empty resource when that column is empty or there is no next half tile), and the
             // workgroup's first half tile counts as seen.  (skip_ht implies flags, i.e. the resource form of the requests.)
-            const int ncol = more ? (ct + ct_step) * 4 + 2 * half : col0;
+            const int ncol = more ? ctn * 4 + 2 * half : col0;
             issue_wt_loads_buf<R, T>(wbase + (size_t)ncol * g.Ph, tbase + (size_t)ncol * g.Ph,
                                      (more && tile2_col_active(fwn, half, 0)) ? col_bytes : 0u, do_upd, j, wr, tr);
             first = false;
@@ -2658,7 +2733,7 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 //  true, nq then holds zeros nobody reads, and the top of the loop requests nothing either)
                 bool next_empty = false;
                 if constexpr (WTBUF && PHASE == 0) next_empty = cflag4 != nullptr && a.zero_fwd != 0 && tile2_half_empty(fwn, half);
-                const Cx<R>* ghn = a.gh + (size_t)b * g.Sh * g.Pw + (size_t)(have_nq ? ct + ct_step : ct) * g.Sh * 4 + 2 * half;
+                const Cx<R>* ghn = a.gh + (size_t)b * g.Sh * g.Pw + (size_t)(have_nq ? ctn : ct) * g.Sh * 4 + 2 * half;
                 const unsigned tbytes = (unsigned)((size_t)g.Sh * 4 - 2 * half) * (unsigned)sizeof(Cx<R>);
                 const Buf bn(ghn, (have_nq && !next_empty) ? tbytes : 0u), bs(gh, tbytes);
 #pragma unroll
@@ -2676,6 +2751,7 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
             }
         }
         fw = fwn;
+        ct = ctn;
     }
     HGS_T(fft.tr_n, 7);
     if constexpr (do_upd) {

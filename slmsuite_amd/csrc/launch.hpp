@@ -15,6 +15,7 @@ template <typename Fam> struct KernelOf;
 #define HGS_BIND_F32(tag, kernel) \
     template <> struct KernelOf<tag> { template <typename R, auto... V> static auto ptr() { return kernel<V...>; } }
 HGS_BIND(KRow, row_kernel);
+HGS_BIND(KRowZ, row_zmask_kernel);
 HGS_BIND(KCol, col_kernel);
 HGS_BIND(KFused, col_fused_kernel);
 HGS_BIND(KTile, col_tile_kernel);
@@ -45,7 +46,8 @@ static inline int launch_instance(dim3 grid, dim3 block, size_t lds, hipStream_t
 }
 
 template <typename R> inline unsigned row_flags(dim3 grid, const RowArgs<R>& a) {
-    return (a.load_mask ? DF_LOAD_MASK : 0u) | (a.store_mask ? DF_STORE_MASK : 0u) | (grid.y > 1 ? DF_BATCH : 0u) | (a.nf_out ? DF_NF_OUT : 0u);
+    return (a.load_mask ? DF_LOAD_MASK : 0u) | (a.store_mask ? DF_STORE_MASK : 0u) | (grid.y > 1 ? DF_BATCH : 0u) | (a.nf_out ? DF_NF_OUT : 0u) |
+           (a.zero_mask ? DF_ZERO_MASK : 0u);
 }
 template <typename R> inline unsigned col_flags(dim3 grid, const ColArgs<R>& a) {
     return (a.col_list ? DF_LIST : 0u) | ((a.col_list ? a.list_xmap : a.col_xmap) ? DF_XMAP : 0u) | (grid.y > 1 ? DF_BATCH : 0u) |

@@ -9,6 +9,9 @@ template <typename R, int N, int NS>
 static int launch_row_pref(dim3 grid, hipStream_t s, const RowArgs<R>& a) {
     constexpr size_t lds = (lds_elems<N>() + N) * sizeof(Cx<R>);
     static_assert(lds > 48 * 1024, "launch_row_pref: the two images need the raised LDS limit");
+#ifdef HGS_REAL_IS_FLOAT
+    if (a.zero_mask != nullptr) return launch_instance<KRowZ, R, N, 2, NS, true, false>(grid, dim3(RowCfg<N>::WG), lds, s, row_flags(grid, a), a);
+#endif
     return launch_instance<KRow, R, N, 2, NS, true, false>(grid, dim3(RowCfg<N>::WG), lds, s, row_flags(grid, a), a);
 }
 
@@ -21,6 +24,15 @@ static int launch_row_one(dim3 grid, hipStream_t s, const RowArgs<R>& a) {
     constexpr size_t lds_need = (size_t)RowCfg<N>::FPW * lds_elems<N>() * sizeof(Cx<R>);
     const bool masked = a.load_mask != nullptr || a.store_mask != nullptr;
     const size_t lds = (NS < 16 && N == 4096 && !masked && lds_need < 48 * 1024) ? (size_t)48 * 1024 : lds_need;
+#ifdef HGS_REAL_IS_FLOAT
+    // (RowArgs::zero_mask: the instances that honour it, MODE 2 only; anywhere else the mask is an error, not ignored)
+    if (a.zero_mask != nullptr) {
+        if constexpr (MODE == 2) return launch_instance<KRowZ, R, N, MODE, NS, false, false>(grid, dim3(RowCfg<N>::WG), lds, s, row_flags(grid, a), a);
+        else return (int)hipErrorInvalidValue;
+    }
+#else
+    if (a.zero_mask != nullptr) return (int)hipErrorInvalidValue;
+#endif
     return launch_instance<KRow, R, N, MODE, NS, false, false>(grid, dim3(RowCfg<N>::WG), lds, s, row_flags(grid, a), a);
 }
 
@@ -29,6 +41,7 @@ template <typename R, int N>
 static int launch_row_n(int mode, dim3 grid, hipStream_t s, const RowArgs<R>& a) {
 #ifdef HGS_REAL_IS_FLOAT
     if constexpr (N == 4096) {
+        // (RowArgs::zero_mask is no load / store mask: every column is read and written, the prefetching form stays)
         if (a.prefetch && mode == 2 && a.load_mask == nullptr && a.store_mask == nullptr)
             return a.shifted ? launch_row_pref<R, N, 8>(grid, s, a) : launch_row_pref<R, N, 16>(grid, s, a);
     }

@@ -12,8 +12,10 @@ static int launch_tile2_one(dim3 grid, hipStream_t s, const ColArgs<float>& a, i
     const unsigned zero_inv = (reads_flags && a.col_flags != nullptr && a.zero_inv) ? DF_ZERO_INV : 0u;
     // (... and, where they skip the inverse, neither load nor transform those columns forward)
     const unsigned zero_fwd = (zero_inv && a.zero_fwd) ? DF_ZERO_FWD : 0u;
+    // (... and, where the row launch before left the zeros of the empty columns in H, walk past empty half tiles)
+    const unsigned prezero = (zero_fwd && a.h_prezeroed) ? DF_PREZERO : 0u;
     return launch_instance<KTile2, float, N, PHASE, NR, RULE, PARK, NXF>(grid, dim3(Tile2Cfg<N>::WG), lds, s,
-                                                                         col_flags(grid, a) | (half_xmap ? DF_XMAP : 0u) | zero_inv | zero_fwd, a, shift, half_xmap);
+                                                                         col_flags(grid, a) | (half_xmap ? DF_XMAP : 0u) | zero_inv | zero_fwd | prezero, a, shift, half_xmap);
 }
 template <int N, int RULE, int NR>
 static int launch_tile2_n(int phase, dim3 grid, hipStream_t s, const ColArgs<float>& a, int shift, int half_xmap) {
