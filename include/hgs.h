@@ -398,7 +398,7 @@ int hgs_sync(hgs_engine* e);
  * HGS_ROW_PREF_BATCH, HGS_TILE_RULE, HGS_MRAF_SPLIT, HGS_MRAF_SPLIT64, HGS_GH2_MASK, HGS_TILE_LIST, HGS_TILE_SHIFT16, HGS_TILE_NR4,
  * HGS_TILE2, HGS_TILE2_MIN_BATCH, HGS_TILE2_PHASE2, HGS_KEEP_G, HGS_FUSED_SHIFT, HGS_MONO_TAB, HGS_MRAF_PRESUM, HGS_PRESUM_ROWS,
  * HGS_PRESUM_BLOCKS, HGS_EMPTY_COL_LOADS, HGS_EMPTY_COL_INVERSE, HGS_EMPTY_COL_FORWARD,
- * HGS_EMPTY_COL_PREZERO -- all default to the tuned path;
+ * HGS_EMPTY_COL_PREZERO, HGS_EMPTY_COL_LIST -- all default to the tuned path;
  * HGS_TRACE_INIT=1 prints where hgs_create spends its time).
  *   HGS_KEEP_G (default 1): the last row launch of a float32 hgs_iterate call leaves G of the next body behind, and the next
  *   call -- or hgs_nearfield2farfield -- on an unchanged phase starts from it.  That G is the loop's own un-rounded phasor
@@ -427,6 +427,13 @@ int hgs_sync(hgs_engine* e);
  *   the empty ones (`prezero`).  Inside one hgs_iterate call only: the first body of a call runs the plain form, the last row
  *   launch of a call leaves G of every column as before, so calls of a single body gain nothing.  HGS_PHASE and HGS_WEIGHTS are
  *   the same bit for bit; 0 has every column launch store its zeros itself (the tests' A/B reference).
+ * HGS_OPT_EMPTY_COL_LIST (default 1; HGS_EMPTY_COL_LIST in the environment): where HGS_OPT_EMPTY_COL_PREZERO acts, the column
+ *   launch walks the POSITIONS of the ascending list of 4-column tiles that hold anything (built on the device with the column
+ *   scan) instead of every tile: pair i of workgroups takes list entries i, i + pairs, ..., so that 32 spot tiles go to 32
+ *   pairs wherever they sit in the farfield (`tile_list` in hgs_dispatch_read); a workgroup without an entry returns at once.
+ *   The weight norm of these launches is summed per half tile (one slot per hologram, tile, half and wave, folded by the row
+ *   launch in a fixed order), so HGS_PHASE and HGS_WEIGHTS are the same bit for bit with the option off, and for every grid
+ *   HGS_TILE2_BLOCKS asks for; 0 keeps the static walk over all tiles (the tests' A/B reference).
  * HGS_OPT_ROCTX (default 0): roctx ranges (hgs_iterate, hgs_nearfield2farfield, hgs_farfield_constraint,
  *   hgs_farfield2nearfield) for rocprofv3 --marker-trace; the roctx library is dlopen'ed on first use.
  * HGS_OPT_KEEP_PREV_PHASE (default 0): a fused hgs_iterate / hgs_iterate_stats call of ONE iteration that rewrites the
@@ -438,7 +445,8 @@ int hgs_sync(hgs_engine* e);
 enum { HGS_OPT_SPARSE_COLUMNS = 1, HGS_OPT_FORCE_STEPWISE = 2, HGS_OPT_TILE_KERNEL = 3, HGS_OPT_SEPARABLE = 4,
        HGS_OPT_SEPARABLE_MIN_SPOTS = 5, HGS_OPT_ROCTX = 6, HGS_OPT_RUN_KERNELS = 7, HGS_OPT_KEEP_PREV_PHASE = 8,
        HGS_OPT_EMPTY_COL_LOADS = 9, HGS_OPT_SEP_WORKGROUPS = 10,
-       HGS_OPT_EMPTY_COL_INVERSE = 11, HGS_OPT_EMPTY_COL_FORWARD = 12, HGS_OPT_EMPTY_COL_PREZERO = 13 };
+       HGS_OPT_EMPTY_COL_INVERSE = 11, HGS_OPT_EMPTY_COL_FORWARD = 12, HGS_OPT_EMPTY_COL_PREZERO = 13,
+       HGS_OPT_EMPTY_COL_LIST = 14 };
 int hgs_set_option(hgs_engine* e, int option, int value);
 
 /* Timing support for bench.py: per-kernel HIP-event timing on the engine stream. */

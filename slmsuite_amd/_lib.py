@@ -21,6 +21,7 @@ OPT_SEP_WORKGROUPS = 10
 OPT_EMPTY_COL_INVERSE = 11
 OPT_EMPTY_COL_FORWARD = 12
 OPT_EMPTY_COL_PREZERO = 13
+OPT_EMPTY_COL_LIST = 14
 
 # array selectors (include/hgs.h)
 (PHASE, AMP, AMP_SCALAR, PROP_KERNEL, TARGET, WEIGHTS, PHASE_FF, FARFIELD, AMP_FF, SPOT_INDEX,

@@ -47,6 +47,9 @@ struct Tuning {
     int empty_col_prezero = 1;  // HGS_EMPTY_COL_PREZERO=0 / HGS_OPT_EMPTY_COL_PREZERO: ... and, where the forward transform is skipped, every
                                 // body of a call stores the zeros of the empty columns itself instead of finding them left by the row
                                 // launch before it (acts only with empty_col_forward; prezero_ok below)
+    int empty_col_list = 1;     // HGS_EMPTY_COL_LIST=0 / HGS_OPT_EMPTY_COL_LIST: ... and, where it finds them left (prezero_ok), a workgroup
+                                // keeps its static walk over ALL tiles instead of walking the positions of the list of tiles that
+                                // hold anything (acts only with empty_col_prezero; tile_list_ok below)
     int sparse = 1;             // HGS_OPT_SPARSE_COLUMNS
     int tile = 1;               // HGS_OPT_TILE_KERNEL (0 forces the per-column kernel at every size: the tests' A/B reference)
 };
@@ -395,6 +398,19 @@ inline bool prezero_ok(const ColumnPlan& cp, const PassFacts& f) {
     if (!t.empty_col_inverse || !t.empty_col_forward || !t.empty_col_prezero) return false;
     if (cp.second_pass || cp.nog || cp.presum || cp.presum_col || cp.dilated_forward || cp.noise_inverse_grid || l.stats || f.stat_groups) return false;
     return cp.join == RowJoin::none;
+}
+// ... and that launch walks the positions of the scan's tile list (ColArgs::tile_list) instead of every tile
+inline bool tile_list_ok(const ColumnPlan& cp, const PassFacts& f) { return prezero_ok(cp, f) && f.tun.empty_col_list != 0; }
+
+// The launches whose weight-norm partials are one slot per (hologram, tile, half, wave) in a buffer of their own
+// (ColArgs::wslots, tile_flags.hpp) instead of one per workgroup in wpartial: the updating launches of the instances of
+// col_tile2_kernel that can receive column flags (WTBUF: 4096 rows, at most five slots, PHASE 0; the register form of a batch
+// or the parked few-active form of one hologram -- launch_tile2_n picks by exactly these facts).  The sum then no longer depends
+// on which workgroup took which half tile.  The engine asks it for the column launch and for the fold of the row launch behind it.
+inline bool wslots_ok(const ColLaunch& l, const PassFacts& f) {
+    if (f.elem != 4 || f.Ph != 4096 || l.family != ColFamily::tile2) return false;
+    if (l.phase_mode != 0 || l.nr > 5 || !l.do_update) return false;
+    return f.B > 1 || l.few_active;
 }
 
 // spot feedback on a sparse target (Engine::iterate_spot_sparse): the fused launch over the spot columns, weight update off

@@ -27,6 +27,7 @@ enum : unsigned {
     DF_QUAD = 2048u,     // pattern_kernel: four windows, each with its own grating (PatArgs::quad)
     DF_PREZERO = 4096u,  // col_tile2_kernel with zero_fwd: H of the empty columns is in place already, empty half tiles are walked past (ColArgs::h_prezeroed)
     DF_ZERO_MASK = 8192u, // row kernel: stores that zero H instead of G in the columns the scan found empty (RowArgs::zero_mask)
+    DF_TILE_LIST = 16384u, // col_tile2_kernel with prezero: the walk runs over the positions of the scan's tile list (ColArgs::tile_list)
 };
 
 struct DispatchSite {

@@ -62,7 +62,7 @@ thread_local DispatchLog* g_dispatch = nullptr;
 // one line per (kernel instance, run-time flags): "family<P0=v0,...> flag ...\tcount\n".  The argument values come from
 // __PRETTY_FUNCTION__ of dispatch_site<Fam, R, V...>: "... [Fam = hgs::KTile, R = float, V = <4096, 1, 6, false, false, 1, 0>]"
 std::string DispatchLog::text() const {
-    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags", "sk_cap", "zero_inv", "zero_fwd", "quad", "prezero", "zero_mask"};
+    static const char* flag_names[] = {"list", "load_mask", "store_mask", "xmap", "batch", "stats", "nf_out", "col_flags", "sk_cap", "zero_inv", "zero_fwd", "quad", "prezero", "zero_mask", "tile_list"};
     std::string out;
     for (const Ent& e : v) {
         std::vector<std::string> vals;
@@ -365,6 +365,13 @@ template <typename R> struct Engine : EngineBase {
     DevBuf<unsigned char> col_active;   // [B][Pw]
     DevBuf<unsigned short> sig_rows;    // [B][Pw] register slots of a column that hold signal pixels (scan_active_cols; col_presum_kernel)
     ColList active;                     // any bit of col_active
+    // col_tile2_kernel, flag-reading instances: the ascending tiles that hold anything per hologram and how many (built with the
+    // scan, refresh_sparse), and the weight-norm slots per (hologram, tile, half, wave) of their updating launches (wslots_ok).
+    // A slot of an EMPTY half tile reads +0 for as long as the scan is current: the buffer is cleared where it is made and with
+    // every scan, a launch that walks past the half tile never writes it, and one that visits it (no flags, an option off)
+    // sums the squares of weights that are all zero -- every pixel of such a column leaves the rule at wave_all_zero.
+    DevBuf<int> tile_list, tile_list_n;       // [B][Pw/4], [B]
+    DevBuf<double> wslots;                    // [B][tile2_wslots(Pw)]
     DevBuf<unsigned short> lane_mask_noise;   // row-kernel view of its bit 4: columns with a NaN target (noise part of single-pass MRAF)
     // the same for the columns the spot integration windows touch (spot feedback / spot statistics)
     DevBuf<unsigned char> col_active_d;
@@ -512,6 +519,7 @@ template <typename R> struct Engine : EngineBase {
         t.empty_col_inverse = env_int("HGS_EMPTY_COL_INVERSE", 1);
         t.empty_col_forward = env_int("HGS_EMPTY_COL_FORWARD", 1);
         t.empty_col_prezero = env_int("HGS_EMPTY_COL_PREZERO", 1);
+        t.empty_col_list = env_int("HGS_EMPTY_COL_LIST", 1);
         return t;
     }
 
@@ -1231,6 +1239,11 @@ template <typename R> struct Engine : EngineBase {
     int run_row_impl(int mode, bool finalize, int load_sparse, int store_sparse, const ColumnPlan* cp, int zero_par = -1) {
         return timed(HGS_K_ROW, [&]() -> int {
             RowArgs<R> a = row_args(finalize, cp ? cp->wpartial_n : 0);
+            // the partials of a launch that left them per half tile (the same predicate as ahead of the column launch): the
+            // row-less block folds the hologram's WHOLE slot range
+            if (finalize && cp && !cp->second_pass && wslots_ok(cp->main, base_facts())) {
+                a.wpartial = wslots; a.n_wpartial = tile2_wslots(g.Pw); a.wslot_fold = 1;
+            }
             a.load_mask = load_sparse == 1 ? active.mask.get() : load_sparse == 2 ? dilated.mask.get() : nullptr;
             a.store_mask = store_sparse == 1 ? active.mask.get() : store_sparse == 2 ? dilated.mask.get() : nullptr;
             if (zero_par >= 0) {
@@ -1292,6 +1305,13 @@ template <typename R> struct Engine : EngineBase {
         return f;
     }
     bool tile_geometry_ok() const { return hgs::tile_geometry_ok(base_facts()); }
+    // the weight-norm slots, every one +0: when they are made and with every column scan (see the buffer's declaration)
+    int clear_wslots() {
+        const size_t n = (size_t)B * tile2_wslots(g.Pw);
+        if (!wslots) { HIPCHK(wslots.alloc_zeroed(n, stream)); return 0; }
+        HIPCHK(hipMemsetAsync(wslots.get(), 0, n * sizeof(double), stream));
+        return 0;
+    }
     // (re)build the active-column list when weights or target changed since the last scan
     int refresh_sparse() {
         if (!state.sparse_dirty()) return 0;
@@ -1330,6 +1350,16 @@ template <typename R> struct Engine : EngineBase {
             }
         }
         if (int e = active.build(col_active, 0xff, B, g.Pw, stream)) return e;
+        // the flag-reading instances of the half-width kernel (fp32, 4096 rows): the list of tiles that hold anything, on the
+        // device and without a synchronisation of its own; the weight-norm slots of what the old scan called non-empty go back to +0
+        if (sizeof(R) == 4 && g.Ph == 4096) {
+            HIPCHK(tile_list.ensure((size_t)B * (g.Pw / 4)));
+            HIPCHK(tile_list_n.ensure((size_t)B));
+            hipLaunchKernelGGL(compact_active_tiles, dim3(B), dim3(256), 0, stream, (const unsigned char*)col_active, g.Pw,
+                               tile_list.get(), tile_list_n.get());
+            HIPCHK(hipGetLastError());
+            if (int e = clear_wslots()) return e;
+        }
         HIPCHK(lane_mask_noise.ensure((size_t)B * (g.Pw / 16)));
         hipLaunchKernelGGL(flag_lane_mask, dim3((g.Pw / 16 + 255) / 256, B), dim3(256), 0, stream, (const unsigned char*)col_active,
                            g.Pw, 4, lane_mask_noise.get());
@@ -1912,7 +1942,8 @@ template <typename R> struct Engine : EngineBase {
     }
     // one launch of the column pass; then_scale: wscale = 1/||w'|| from its partials right after it (reduce_to_scale)
     // prezeroed: the row launch immediately before, in this call, stored the zeros of the empty columns (prezero_ok)
-    int launch_column(const ColLaunch& l, const CParams<R>& cprm, bool then_scale = false, bool prezeroed = false) {
+    // list_walk: ... and this launch walks the scan's tile list (tile_list_ok)
+    int launch_column(const ColLaunch& l, const CParams<R>& cprm, bool then_scale = false, bool prezeroed = false, bool list_walk = false) {
         return timed(HGS_K_COL_FUSED, [&]() -> int {
             ColArgs<R> a = col_args();
             a.cp = cprm;
@@ -1938,6 +1969,13 @@ template <typename R> struct Engine : EngineBase {
                 a.zero_inv = tun.empty_col_inverse ? 1 : 0;
                 a.zero_fwd = (a.zero_inv && tun.empty_col_forward) ? 1 : 0;      // (the forward skip rests on the inverse skip)
                 a.h_prezeroed = (a.zero_fwd && prezeroed) ? 1 : 0;
+                if (a.h_prezeroed && list_walk && tile_list && tile_list_n) { a.tile_list = tile_list; a.tile_list_n = tile_list_n; }
+            }
+            // weight-norm partials per half tile instead of per workgroup; the row launch behind it folds them (run_row_impl)
+            if (wslots_ok(l, base_facts())) {
+                if (then_scale) return fail(HGS_ERR_STATE, "weight-norm slots ahead of a per-workgroup reduction");
+                if (!wslots) { if (int e = clear_wslots()) return e; }
+                a.wslots = wslots;
             }
             a.few_active = l.few_active ? 1 : 0;
             if (l.family == ColFamily::tile_split || l.family == ColFamily::tile_split_stats) { a.gh2 = gh2; a.gh2_sparse = l.gh2_sparse ? 1 : 0; }
@@ -2108,7 +2146,7 @@ template <typename R> struct Engine : EngineBase {
             if (cp.dilated_forward) { if (int e = launch_dilated_forward()) return e; }
             if (int e = launch_prepass(cp, cprm)) return e;
             if (cp.nog) { if (int e = launch_column(cp.nog_pass, cprm)) return e; }
-            if (int e = launch_column(cp.main, cprm, cp.scale_after_main, gh_prezeroed)) return e;
+            if (int e = launch_column(cp.main, cprm, cp.scale_after_main, gh_prezeroed, gh_prezeroed && tile_list_ok(cp, f))) return e;
             gh_prezeroed = false;
             if (cp.second_pass) { if (int e = launch_column(cp.second, cprm)) return e; }
             if (int e = launch_noise_inverse(cp)) return e;
@@ -2372,6 +2410,7 @@ template <typename R> struct Engine : EngineBase {
             case HGS_OPT_EMPTY_COL_INVERSE: tun.empty_col_inverse = value ? 1 : 0; return 0;
             case HGS_OPT_EMPTY_COL_FORWARD: tun.empty_col_forward = value ? 1 : 0; return 0;
             case HGS_OPT_EMPTY_COL_PREZERO: tun.empty_col_prezero = value ? 1 : 0; return 0;
+            case HGS_OPT_EMPTY_COL_LIST: tun.empty_col_list = value ? 1 : 0; return 0;
             case HGS_OPT_KEEP_PREV_PHASE: opt_prev_phase = value ? 1 : 0; if (!value) state.prev_phase_dropped(); return 0;
             case HGS_OPT_ROCTX:
                 if (value && !g_roctx.load()) return fail(HGS_ERR_UNSUPPORTED, "no roctx library (librocprofiler-sdk-roctx / libroctx64) found");

@@ -201,6 +201,42 @@ __device__ __forceinline__ double wave_sum(double v) {
     }
     return v;
 }
+// The sum of a double over the 64 lanes of a FULL wave by DPP adds -- no LDS, no barrier: butterflies inside a quad, the two
+// mirrors of a row of 16, then the four row sums read as scalars and added in a fixed order.  Every lane ends with the same
+// value, which depends on the 64 inputs alone.
+template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, true), __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
+}
+__device__ __forceinline__ double wave64_sum_dpp(double v) {
+    v += dpp_f64<0xB1>(v);       // quad_perm [1, 0, 3, 2]
+    v += dpp_f64<0x4E>(v);       // quad_perm [2, 3, 0, 1]
+    v += dpp_f64<0x141>(v);      // row_half_mirror: the other quad of the eight
+    v += dpp_f64<0x140>(v);      // row_mirror: the other eight of the row
+    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+// The fold over the weight-norm slots of one hologram (tile_flags.hpp; n doubles, n even, 16-byte aligned): every lane of the
+// workgroup takes 16-byte loads, eight of them in flight together, and adds what they bring in the order of the loads -- an
+// association that depends on n and the workgroup's size alone.  The caller sums the lanes (block_sum).
+__device__ __forceinline__ double fold_wslots(const double* slots, int n) {
+    const double2* p = reinterpret_cast<const double2*>(slots);
+    const int n2 = n >> 1, nt = (int)blockDim.x, tid = (int)threadIdx.x;
+    double s = 0;
+    for (int i0 = 0; i0 < n2; i0 += 8 * nt) {
+        double2 q[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = i0 + u * nt + tid;
+            q[u] = i < n2 ? p[i] : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += q[u].x + q[u].y;
+    }
+    return s;
+}
 // scratch: at least 16 doubles of LDS not in use by anyone else at the call
 __device__ __forceinline__ double block_sum(double v, double* scratch) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
@@ -538,8 +574,10 @@ template <typename R> struct RowArgs {
     // weight-norm finalisation carried by block (0, b): wscale[b] = 1/sqrt(sum partial[b][:])
     const double* wpartial;
     int n_wpartial;
+    int wslot_fold;      // fp32: wpartial / n_wpartial are the weight-norm SLOTS of a hologram (ColArgs::wslots, all of them: an
+                         // unvisited one reads +0), folded by fold_wslots -- the same bits whatever schedule filled them
     R* wscale;
-    int xcd_map;         // rows 4q..4q+3 (which share 128-B lines of GH) on one XCD at the same time
+    int xcd_map;        // rows 4q..4q+3 (which share 128-B lines of GH) on one XCD at the same time
     int n_row_blocks;    // workgroups that own rows (the grid may hold one more, row-less, for the weight norm)
     int shifted, m0;     // shifted form (row_kernel NS < 16): on / register slot of the first SLM column, c0 / (Pw / 16)
     int prefetch;        // row_kernel PREF: workgroups walk several rows each, the next row's H on its way into LDS
@@ -608,6 +646,8 @@ __device__ __forceinline__ void row_body(const RowArgs<R>& a) {
     //  reduction does not lengthen any row's critical path)
     if (a.wpartial != nullptr && blockIdx.x == gridDim.x - 1) {
         double s = 0;
+        if (sizeof(R) == 4 && a.wslot_fold) s = fold_wslots(a.wpartial + (size_t)b * a.n_wpartial, a.n_wpartial);
+        else
         for (int i = tid; i < a.n_wpartial; i += blockDim.x) s += a.wpartial[(size_t)b * a.n_wpartial + i];
         double* scratch = reinterpret_cast<double*>(smem);
         s = block_sum(s, scratch);
@@ -1117,6 +1157,10 @@ template <typename R> struct ColArgs {
     int h_prezeroed;       // ... (HGS_OPT_EMPTY_COL_PREZERO, only with col_flags and zero_fwd) and the row launch ahead of this one has
                            // already left those zeros in the empty columns of gh (RowArgs::zero_mask): a workgroup walks from one
                            // non-empty half tile to the next and an empty one costs a scalar look at its flag word
+    const int* tile_list;  // ... (HGS_OPT_EMPTY_COL_LIST, only with h_prezeroed) [batch][Pw/4]: the ascending tiles whose flag word has bit 0
+    const int* tile_list_n;  // set in any byte, and [batch] how many there are (built with the scan): the walk runs over list positions
+    double* wslots;        // col_tile2_kernel, the updating flag-reading instances (wslots_ok): [batch][tile2_wslots(Pw)] sum w'^2 per
+                           // tile, half and wave (tile_flags.hpp) instead of one partial per workgroup in wpartial
     int fnr;               // col_fused_kernel: register slots the shifted SLM rows occupy (0 = the unshifted kernel, NRS = 16)
     int fshift;            // col_fused_kernel<..., NRS < 16> (float64, >= 4096 rows): circular shift of the transform input, a
                            // multiple of 16 rows (shift theorem, as in col_tile_kernel): the SLM rows occupy slots 0 .. NRS - 1
@@ -2409,32 +2453,11 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
         __syncthreads();
     }
 #endif
-    using Sel = FftSel<R, N, true>;
-    typename Sel::type fft;
-    fft.init(a.tw, j);
-    const CParams<R> cp = a.cp;
     constexpr bool do_upd = RULE == 1;
-    const int js = Sel::space_lane(j);
-    const R sgn = (j & 1) ? (R)-1 : (R)1;
-    const R sgs = (js & 1) ? (R)-1 : (R)1;
-    const size_t P = (size_t)g.Ph * g.Pw;
-    const R wsc = a.wscale[b];
-    Cx<R> om = a.tw[(j * shift) & (N - 1)];            // shift-theorem factor (see col_tile_kernel), sign and ortho scale folded in
-    om = om * (sgn * a.scale);
-    const int r_lane = js + shift - g.r0;              // SLM row of slot m is r_lane + m*T
     const int ntiles = g.Pw / 4;
-    R acc_w = 0;
 
-    Cx<R> v[16];
-    // the half tile, one array per column and component: selected by the (uniform) column of the pass with v_cndmask -- a
-    // run-time index into [NR][2] arrays put them on the stack (96 bytes of scratch), unrolling the two passes made the
-    // scheduler interleave them (23 .. 187 spilled registers)
-    R g0x[PARK ? 1 : NR], g0y[PARK ? 1 : NR], g1x[PARK ? 1 : NR], g1y[PARK ? 1 : NR];
-    Cx<R>* park = reinterpret_cast<Cx<R>*>(scratch + SCRATCH_DOUBLES) + j;     // PARK: slot m of this lane at park[m * T]
-    R wr[16], tr[16];
-    const R* wbase = a.w + (size_t)b * P;
-    const R* tbase = a.t + (size_t)b * P;
-
+    // (the schedule and the first look at the flags come first: a workgroup that the tile list leaves without work returns
+    //  ahead of the twiddle loads of fft.init)
     // schedule: CPAR = 2 -- a workgroup owns whole tiles, group g their half g.  CPAR = 1 -- a workgroup owns half tiles;
     // with half_xmap (gridDim.x a multiple of 16) workgroups (xcd, 2 i) and (xcd, 2 i + 1) take the two halves of one tile
     // (workgroups run round-robin over the 8 XCDs -- a speed-only assumption, as in row_kernel)
@@ -2468,17 +2491,63 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
     const bool wt_buf = WTBUF && (NXF || cflag4 != nullptr);        // (uniform; NXF: a constant)
     // a.h_prezeroed (with the flags and a.zero_fwd): the row launch before this one stored the zeros of the empty columns, so an
     // empty half tile has nothing left to do.  The workgroup keeps its static schedule (ct0, ct_step, half) but visits only the
-    // half tiles that are not empty, in the same order -- acc_w sums the same columns as before -- and `more`, fwn, the rows
+    // half tiles that are not empty, in the same order -- the weight norm is summed per half tile (WSLOT below) -- and `more`, fwn, the rows
     // requested ahead and the weight / target chain refer to the NEXT NON-EMPTY half tile (ctn).  Finding it is a scalar walk
     // over flag words, the same in all four waves, outside every barrier region; skip_ht is then never true in the loop.
     bool prez = false;
     if constexpr (WTBUF && PHASE == 0) prez = cflag4 != nullptr && a.zero_fwd != 0 && a.h_prezeroed != 0;
     auto flag_word = [&](int i) { return uniform_load_i32(cflag4 + i); };
+    // a.tile_list (with a.h_prezeroed): the same walk over the POSITIONS of the scan's list of tiles that hold anything -- `pos`
+    // counts positions from ct0 in steps of ct_step below the list's length, the tile is one scalar load, a position whose `half`
+    // is empty is passed.  32 spot tiles then go to 32 workgroup pairs instead of wherever tile % ct_step puts them.  What is
+    // summed into which weight-norm slot does not depend on the walk (wslot below), so the two walks leave the same bytes.
+    const int* tlist = nullptr;
+    int nlist = 0, pos = ct0;
+    if constexpr (WTBUF && PHASE == 0) {
+        if (prez && a.tile_list != nullptr) {
+            tlist = a.tile_list + (size_t)b * ntiles;
+            nlist = uniform_load_i32(a.tile_list_n + b);
+        }
+    }
+    auto list_at = [&](int p) { return uniform_load_i32(tlist + p); };
     int ct = ct0;
     if constexpr (WTBUF) {
-        if (prez) ct = tile2_next_nonempty(flag_word, ct0, ct_step, ntiles, half, &fw);
+        if (tlist != nullptr) {
+            ct = tile2_next_listed(list_at, flag_word, &pos, ct_step, nlist, ntiles, half, &fw);
+            if (ct >= ntiles) return;          // (uniform; nothing of this workgroup's to write: its slots belong to half tiles)
+        } else if (prez) ct = tile2_next_nonempty(flag_word, ct0, ct_step, ntiles, half, &fw);
         else if (cflag4 != nullptr && ct0 < ntiles) fw = uniform_load_i32(cflag4 + ct0);
     }
+    using Sel = FftSel<R, N, true>;
+    typename Sel::type fft;
+    fft.init(a.tw, j);
+    const CParams<R> cp = a.cp;
+    const int js = Sel::space_lane(j);
+    const R sgn = (j & 1) ? (R)-1 : (R)1;
+    const R sgs = (js & 1) ? (R)-1 : (R)1;
+    const size_t P = (size_t)g.Ph * g.Pw;
+    const R wsc = a.wscale[b];
+    Cx<R> om = a.tw[(j * shift) & (N - 1)];            // shift-theorem factor (see col_tile_kernel), sign and ortho scale folded in
+    om = om * (sgn * a.scale);
+    const int r_lane = js + shift - g.r0;              // SLM row of slot m is r_lane + m*T
+    R acc_w = 0;
+    // Weight norm of the instances that can receive flags (a.wslots, the engine's wslots_ok): every half tile leaves ITS sum
+    // w'^2, one double per wave, in the slot of (hologram, tile, half, wave) -- acc_w starts at zero in every half tile and is
+    // summed over the wave's 64 lanes by DPP adds, no LDS, no barrier -- so the row launch's fold over the slots gives the same
+    // bits whichever workgroup took which half tile.  A half tile nobody visits (empty, walked past) keeps the +0 its slot was
+    // cleared to with the scan; a visited empty one would add up nothing but zeros (every pixel leaves at wave_all_zero).
+    // (the launcher refuses such an instance without the buffer)
+    constexpr bool WSLOT = WTBUF && PHASE == 0 && do_upd;
+
+    Cx<R> v[16];
+    // the half tile, one array per column and component: selected by the (uniform) column of the pass with v_cndmask -- a
+    // run-time index into [NR][2] arrays put them on the stack (96 bytes of scratch), unrolling the two passes made the
+    // scheduler interleave them (23 .. 187 spilled registers)
+    R g0x[PARK ? 1 : NR], g0y[PARK ? 1 : NR], g1x[PARK ? 1 : NR], g1y[PARK ? 1 : NR];
+    Cx<R>* park = reinterpret_cast<Cx<R>*>(scratch + SCRATCH_DOUBLES) + j;     // PARK: slot m of this lane at park[m * T]
+    R wr[16], tr[16];
+    const R* wbase = a.w + (size_t)b * P;
+    const R* tbase = a.t + (size_t)b * P;
     // PARK: the rows of the workgroup's NEXT half tile are requested BEFORE the stores of the current one (vmcnt retires in order:
     // behind the stores, the wait for the new rows also waited for the stores to be acknowledged -- tools/microbench/trace_tile2:
     // 6.3 k cycles per half tile); they travel in the registers the finished tile has just freed
@@ -2524,14 +2593,19 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
         }
         const int col0 = ct * 4 + 2 * half;
         // the workgroup's next half tile: ct + ct_step, or with a.h_prezeroed the next one that is not empty (>= ntiles: none)
+        // (with a.tile_list: the tile of the next list position it owns whose `half` is not empty)
         int ctn = ct + ct_step;
         if constexpr (WTBUF) {
-            if (prez) ctn = tile2_next_nonempty(flag_word, ctn, ct_step, ntiles, half, &fwn);
+            if (tlist != nullptr) {
+                pos += ct_step;
+                ctn = tile2_next_listed(list_at, flag_word, &pos, ct_step, nlist, ntiles, half, &fwn);
+            } else if (prez) ctn = tile2_next_nonempty(flag_word, ctn, ct_step, ntiles, half, &fwn);
             else if (cflag4 != nullptr && ctn < ntiles) fwn = uniform_load_i32(cflag4 + ctn);
         }
         const bool more = ctn < ntiles;
         float4 outq[PARK ? NR : 1];
         if (!skip_ht) {
+        if constexpr (WSLOT) acc_w = 0;
 #pragma unroll
         for (int m = 0; m < NR; ++m) {
             const int r = r_lane + m * T;
@@ -2698,6 +2772,12 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
                 outq[m] = make_float4(h0.x, h0.y, h1.x, h1.y);
             }
         }
+        if constexpr (WSLOT) {
+            // this half tile's sum w'^2, per wave; ahead of the row requests below (vmcnt retires in order): on its way with them, it
+            // is acknowledged by the time the new rows arrive, and the H stores stay the youngest
+            const double s = wave64_sum_dpp((double)acc_w);
+            if ((tid & 63) == 0) a.wslots[(size_t)b * tile2_wslots(g.Pw) + tile2_wslot(ct, half, tid >> 6)] = s;
+        }
         } else {
             // the empty half tile: H of both columns is the +0 of the skipped inverse times the lane's sign and scale, exactly what
             // the column loop leaves for an empty column; the stores below are the ones every half tile issues
@@ -2754,7 +2834,7 @@ __global__ __launch_bounds__(Tile2Cfg<N>::WG, (N >= 4096 ? 3 : 2)) void col_tile
         ct = ctn;
     }
     HGS_T(fft.tr_n, 7);
-    if constexpr (do_upd) {
+    if constexpr (do_upd && !WSLOT) {      // (WSLOT: every half tile has left its own)
         const double s = block_sum((double)acc_w, scratch);
         if (tid == 0) a.wpartial[(size_t)b * gridDim.x + blockIdx.x] = s;
     }
@@ -3355,6 +3435,35 @@ static __global__ void compact_active_cols(const unsigned char* active, int Pw, 
         for (int m = 0; m < 16; ++m) m16 |= (unsigned)((active[(size_t)b * Pw + j + m * T] & mask) != 0) << m;
         lane_mask[(size_t)b * T + j] = (unsigned short)m16;
     }
+}
+
+// ... and of the 4-column tiles that hold anything: the ascending list of tiles whose flag word has bit 0 set in any byte, and
+// its length (ColArgs::tile_list: col_tile2_kernel walks its positions).  One workgroup per hologram, as above.
+static __global__ void compact_active_tiles(const unsigned char* active, int Pw, int* list, int* n_listed) {
+    __shared__ int base;
+    __shared__ int wsum[16];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6, ntiles = Pw / 4;
+    const int* word = reinterpret_cast<const int*>(active + (size_t)b * Pw);
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    for (int t0 = 0; t0 < ntiles; t0 += blockDim.x) {
+        const int t = t0 + threadIdx.x;
+        const bool on = t < ntiles && tile2_listed(word[t]);
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(on);
+        if (lane == 0) wsum[wid] = __builtin_popcountll(m);
+        __syncthreads();
+        int off = base;
+        for (int k = 0; k < wid; ++k) off += wsum[k];
+        if (on) list[(size_t)b * ntiles + off + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = t;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int tot = 0;
+            for (int k = 0; k < nw; ++k) tot += wsum[k];
+            base += tot;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) n_listed[b] = base;
 }
 
 // WGS-Nogrette on the fused path: nog[b] = -1 / nanmean(fc) from the column kernel's partial sums; columns the

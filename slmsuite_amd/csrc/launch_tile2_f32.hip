@@ -14,8 +14,13 @@ static int launch_tile2_one(dim3 grid, hipStream_t s, const ColArgs<float>& a, i
     const unsigned zero_fwd = (zero_inv && a.zero_fwd) ? DF_ZERO_FWD : 0u;
     // (... and, where the row launch before left the zeros of the empty columns in H, walk past empty half tiles)
     const unsigned prezero = (zero_fwd && a.h_prezeroed) ? DF_PREZERO : 0u;
+    // (... over the positions of the scan's tile list where it comes along)
+    const unsigned tile_list = (prezero && a.tile_list != nullptr && a.tile_list_n != nullptr) ? DF_TILE_LIST : 0u;
+    // (the updating ones among them leave their weight-norm partials in slots per half tile: column_plan.hpp, wslots_ok)
+    if (reads_flags && RULE == 1 && a.wslots == nullptr) return (int)hipErrorInvalidValue;
     return launch_instance<KTile2, float, N, PHASE, NR, RULE, PARK, NXF>(grid, dim3(Tile2Cfg<N>::WG), lds, s,
-                                                                         col_flags(grid, a) | (half_xmap ? DF_XMAP : 0u) | zero_inv | zero_fwd | prezero, a, shift, half_xmap);
+                                                                         col_flags(grid, a) | (half_xmap ? DF_XMAP : 0u) | zero_inv | zero_fwd | prezero | tile_list,
+                                                                         a, shift, half_xmap);
 }
 template <int N, int RULE, int NR>
 static int launch_tile2_n(int phase, dim3 grid, hipStream_t s, const ColArgs<float>& a, int shift, int half_xmap) {

@@ -37,4 +37,32 @@ HGS_FLAGS_HD inline int tile2_next_nonempty(Load&& load, int ct, int ct_step, in
     return ct;
 }
 
+// The same walk over the POSITIONS of the ascending list of tiles that hold anything (any byte of the flag word with bit 0 set;
+// `nlist` entries, `list(p)` gives entry p): the workgroup owns positions *pos, *pos + step, ... below nlist and half `half` of
+// the tile each of them names.  Stops at the first position whose half is not empty: returns that TILE, leaves its flag word in
+// *fw and the position in *pos; or returns ntiles (and *fw untouched, *pos >= nlist) when none is left.  A listed tile has at
+// least one non-empty half, so of the two workgroups that share a position at least one stops there; with no more listed tiles
+// than workgroup pairs nobody owns two.  Scalars throughout, like tile2_next_nonempty (tests/tile_list_host.cpp walks both).
+// (step >= 1)
+template <typename List, typename Load>
+HGS_FLAGS_HD inline int tile2_next_listed(List&& list, Load&& load, int* pos, int step, int nlist, int ntiles, int half, int* fw) {
+    int p = *pos;
+    while (p < nlist) {
+        const int t = list(p);
+        const int w = load(t);
+        if (!tile2_half_empty(w, half)) { *fw = w; *pos = p; return t; }
+        p += step;
+    }
+    *pos = p;
+    return ntiles;
+}
+// a tile belongs on that list
+HGS_FLAGS_HD constexpr bool tile2_listed(int fw) { return ((unsigned)fw & 0x01010101u) != 0u; }
+
+// Weight-norm slots of the half-width kernel's flag-reading instances: one double per hologram, tile, half and wave, indexed by
+// WHAT was summed and never by who summed it, so that sum w'^2 does not depend on the schedule.
+constexpr int TILE2_WSLOT_WAVES = 4;       // waves of a 4096-row workgroup (256 lanes)
+HGS_FLAGS_HD constexpr int tile2_wslots(int Pw) { return Pw / 4 * 2 * TILE2_WSLOT_WAVES; }      // per hologram
+HGS_FLAGS_HD constexpr int tile2_wslot(int tile, int half, int wave) { return (tile * 2 + half) * TILE2_WSLOT_WAVES + wave; }
+
 }  // namespace hgs

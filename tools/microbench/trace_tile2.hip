@@ -22,10 +22,11 @@ int main() {
     constexpr int N = 4096, T = N / 16;
     Geo g{N, N, 1152, 1920, (N - 1152) / 2, (N - 1920) / 2, 1, T};
     const size_t P = (size_t)N * N;
-    Rt *w, *t, *wscale; Ct *gh, *tw; double *wp, *fp;
+    Rt *w, *t, *wscale; Ct *gh, *tw; double *wp, *fp, *ws;
     hipMalloc(&w, P * sizeof(Rt)); hipMalloc(&t, P * sizeof(Rt));
     hipMalloc(&gh, (size_t)g.Sh * g.Pw * sizeof(Ct)); hipMalloc(&tw, N * sizeof(Ct)); hipMalloc(&wscale, sizeof(Rt));
     hipMalloc(&wp, 4096 * 8); hipMalloc(&fp, (size_t)2048 * 1024 * 8);
+    hipMalloc(&ws, (size_t)tile2_wslots(N) * 8); hipMemset(ws, 0, (size_t)tile2_wslots(N) * 8);   // (the register form's weight-norm slots)
     std::vector<Ct> htw(N);
     for (int i = 0; i < N; ++i) htw[i] = (Ct){(Rt)cos(-2 * M_PI * i / N), (Rt)sin(-2 * M_PI * i / N)};
     hipMemcpy(tw, htw.data(), N * sizeof(Ct), hipMemcpyHostToDevice);
@@ -41,7 +42,7 @@ int main() {
     hipMemcpy(w, hw.data(), P * sizeof(Rt), hipMemcpyHostToDevice); hipMemcpy(t, ht.data(), P * sizeof(Rt), hipMemcpyHostToDevice);
     hipMemcpy(gh, hg.data(), hg.size() * sizeof(Ct), hipMemcpyHostToDevice); hipMemcpy(wscale, &one, sizeof(Rt), hipMemcpyHostToDevice);
     ColArgs<Rt> ca{};
-    ca.g = g; ca.gh = gh; ca.w = w; ca.t = t; ca.wscale = wscale; ca.wpartial = wp; ca.fpartial = fp; ca.tw = tw;
+    ca.g = g; ca.gh = gh; ca.w = w; ca.t = t; ca.wscale = wscale; ca.wpartial = wp; ca.wslots = ws; ca.fpartial = fp; ca.tw = tw;
     ca.scale = (Rt)(1.0 / sqrt((double)N));
     ca.cp.method = M_LEONARDO; ca.cp.do_update = 1; ca.cp.p_exp = (Rt)0.8; ca.cp.inv_fnorm = 1;
     const int shift = (g.r0 / 16) * 16;
