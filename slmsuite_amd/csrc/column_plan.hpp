@@ -1,6 +1,6 @@
 // What one iteration of the fused loop launches, decided in one place: plan_column_pass() maps plain facts (geometry,
 // the iteration's flags, the A/B switches, the column counts of the last scan) to the launches of the column pass and
-// what the row launch after it must do.  Pure host C++ -- no HIP, no engine state, no device -- so that the table can be
+// what the row launch after it must do (plan_row_close()).  Pure host C++ -- no HIP, no engine state, no device -- so that the table can be
 // read here and tested without a GPU (tests/test_column_plan.py); Engine::iterate() fills the facts, acquires what the
 // plan lists and executes it.
 #pragma once
@@ -46,10 +46,10 @@ struct Tuning {
                                 // transforms them forward although nothing reads the result (acts only with empty_col_inverse)
     int empty_col_prezero = 1;  // HGS_EMPTY_COL_PREZERO=0 / HGS_OPT_EMPTY_COL_PREZERO: ... and, where the forward transform is skipped, every
                                 // body of a call stores the zeros of the empty columns itself instead of finding them left by the row
-                                // launch before it (acts only with empty_col_forward; prezero_ok below)
-    int empty_col_list = 1;     // HGS_EMPTY_COL_LIST=0 / HGS_OPT_EMPTY_COL_LIST: ... and, where it finds them left (prezero_ok), a workgroup
+                                // launch before it (acts only with empty_col_forward; ColumnPlan::accepts_prezeroed)
+    int empty_col_list = 1;     // HGS_EMPTY_COL_LIST=0 / HGS_OPT_EMPTY_COL_LIST: ... and, where it finds them left, a workgroup
                                 // keeps its static walk over ALL tiles instead of walking the positions of the list of tiles that
-                                // hold anything (acts only with empty_col_prezero; tile_list_ok below)
+                                // hold anything (acts only with empty_col_prezero; EmptyCols::list_walk)
     int sparse = 1;             // HGS_OPT_SPARSE_COLUMNS
     int tile = 1;               // HGS_OPT_TILE_KERNEL (0 forces the per-column kernel at every size: the tests' A/B reference)
 };
@@ -66,6 +66,8 @@ struct PassFacts {
     bool w_unit = false;            // the stored weights are normalised by wscale (Engine::w_unit)
     bool sparse_enabled = false;    // the column pass walks the list of active columns
     bool sparse_tiles = false, sparse_dirty = true;
+    bool gh_prezeroed = false;      // the row launch before this body, in this call, stored the zeros of the empty columns instead of
+                                    // their G (RowClose::zero_par of the body before)
     bool w_outside_scan = false;    // a kernel that the scan does not see may have written a weight into a column it found empty
                                     // (the N-vector rule of the spot feedback modes writes at the spot pixels, whatever the target holds)
     int n_active_min = 0, n_active_max = 0, n_noise_max = 0, n_signal_max = 0;
@@ -77,6 +79,15 @@ struct PassFacts {
 enum class ColFamily { fused, fused_rule1, fused_rule2, fused_stats, tile, tile_rule, tile_rule_listed, tile_stats,
                        tile_extras, tile_extras_stats, tile_split, tile_split_stats, tile_presum, tile2 };
 
+// How a launch of col_tile2_kernel treats the columns the scan found empty: a ladder, each level on only where the one before
+// it is, and none without the scan's flags (ColLaunch::col_flags).  One switch of Tuning::empty_col_* per level.
+struct EmptyCols {
+    bool skip_inverse = false;      // no rule block and no inverse transform (ColArgs::zero_inv)
+    bool skip_forward = false;      // ... no load and no forward transform either; an empty half tile only stores zeros (zero_fwd)
+    bool prezeroed = false;         // ... the zeros are in place already, empty half tiles are walked past (h_prezeroed)
+    bool list_walk = false;         // ... along the scan's list of the tiles that hold anything (tile_list)
+};
+
 struct ColLaunch {
     ColFamily family = ColFamily::fused;
     int phase_mode = 0;   // 0 = phase taken from the field, 1 = ... and stored, 2 = stored phase used
@@ -86,6 +97,11 @@ struct ColLaunch {
     int nr = 0, shift = 0;          // tile families: register slots of the SLM rows, row shift
     int grid = 0;                   // workgroups per hologram
     bool listed = false, list_xmap = false, half_xmap = false, few_active = false, gh2_sparse = false, col_flags = false;
+    EmptyCols empty;                // (tile2 only)
+    // weight-norm partials one slot per (hologram, tile, half, wave) in a buffer of their own (ColArgs::wslots, tile_flags.hpp)
+    // instead of one per workgroup in wpartial, so that the sum no longer depends on which workgroup took which half tile
+    // (tile2 only); the row launch behind it folds them (RowClose::wslot_fold)
+    bool wslots = false;
     bool nog_pass = false, use_nog = false, weights_only = false, split64 = false;
     int do_update = 0;
     int stats = 0;                  // ColArgs::do_stats: statistics groups this launch accumulates
@@ -112,6 +128,12 @@ struct ColumnPlan {
     bool gh2_mask = false;          // ... the joining launch reads gh2 in the noise columns only
     int last_mode = 1;              // MODE of the call's last row launch: 3 also leaves G of the next body behind
     int wpartial_n = 0;             // partials the last column launch left (weight norm; statistics)
+    // The row launch BEFORE this body may store the zero H of the empty columns instead of their G (RowClose::zero_par) and the
+    // main launch then walks past empty half tiles (main.empty.prezeroed): the half-width kernel with the scan's flags (a current
+    // scan, no weight written behind it, no column list, at most five slots: column_launch), the instance that reads them (PHASE 0,
+    // 4096 rows), every empty-column switch up to empty_col_prezero on, and nothing else in the body that reads or writes gh -- no
+    // second pass, Nogrette sum, pre-pass or in-pass statistics
+    bool accepts_prezeroed = false;
     // buffers the plan needs
     bool need_gh2 = false, need_ffb = false, need_dpartial = false, need_nog_dev = false;
 };
@@ -239,6 +261,29 @@ inline Scans scans_needed(const PassFacts& f) {
     return Scans{m.split64, m.presum_col, m.presum};
 }
 
+// ---- the planner's own predicates on a launch / a plan (column_launch() and plan_column_pass() store what they say in
+// ColLaunch::wslots, ColumnPlan::accepts_prezeroed and EmptyCols::list_walk; the engine reads those fields, never these) ----
+// the updating launches of the instances of col_tile2_kernel that can receive column flags (WTBUF: 4096 rows, at most five
+// slots, PHASE 0; the register form of a batch or the parked few-active form of one hologram -- launch_tile2_n picks by
+// exactly these facts)
+inline bool wslots_ok(const ColLaunch& l, const PassFacts& f) {
+    if (f.elem != 4 || f.Ph != 4096 || l.family != ColFamily::tile2) return false;
+    if (l.phase_mode != 0 || l.nr > 5 || !l.do_update) return false;
+    return f.B > 1 || l.few_active;
+}
+// ColumnPlan::accepts_prezeroed (see there), of a plan whose launches and row join are set
+inline bool prezero_ok(const ColumnPlan& cp, const PassFacts& f) {
+    const Tuning& t = f.tun;
+    const ColLaunch& l = cp.main;
+    if (f.elem != 4 || f.Ph != 4096) return false;
+    if (l.family != ColFamily::tile2 || !l.col_flags || l.phase_mode != 0) return false;
+    if (!t.empty_col_inverse || !t.empty_col_forward || !t.empty_col_prezero) return false;
+    if (cp.second_pass || cp.nog || cp.presum || cp.presum_col || cp.dilated_forward || cp.noise_inverse_grid || l.stats || f.stat_groups) return false;
+    return cp.join == RowJoin::none;
+}
+// ... and the launch that finds the zeros walks the positions of the scan's tile list instead of every tile
+inline bool tile_list_ok(const ColumnPlan& cp, const PassFacts& f) { return prezero_ok(cp, f) && f.tun.empty_col_list != 0; }
+
 // one launch of the main column pass: pass -1 = the Nogrette sum, 0 = the main launch, 1 = the second pass of the two-pass form
 inline ColLaunch column_launch(const PassFacts& f, const MrafForms& m, const ColumnPlan& cp, int pass) {
     const Tuning& t = f.tun;
@@ -295,6 +340,9 @@ inline ColLaunch column_launch(const PassFacts& f, const MrafForms& m, const Col
         // (4096 rows, at most five slots: the instances of col_tile2_kernel that read them, WTBUF)
         l.col_flags = l.few_active && f.Ph == 4096 && l.nr <= 5 && t.empty_col_loads && !f.w_outside_scan;
         l.half_xmap = f.Ph >= 4096 && t2 % 16 == 0;
+        l.empty.skip_inverse = l.col_flags && t.empty_col_inverse;
+        l.empty.skip_forward = l.empty.skip_inverse && t.empty_col_forward;
+        l.wslots = wslots_ok(l, f);
     } else if (m.tile_path) {
         l.grid = tile_grid;
         const bool extras = f.mraf_enabled || l.nog_pass || l.weights_only;
@@ -381,36 +429,51 @@ inline ColumnPlan plan_column_pass(const PassFacts& f) {
     cp.need_ffb = m.split64;
     cp.need_dpartial = m.presum || m.presum_col;
     cp.need_nog_dev = cp.nog;
+    cp.accepts_prezeroed = prezero_ok(cp, f);
+    cp.main.empty.prezeroed = cp.accepts_prezeroed && f.gh_prezeroed;
+    cp.main.empty.list_walk = cp.main.empty.prezeroed && tile_list_ok(cp, f);
     return cp;
 }
 
-// The row launch that closes body i may store the zero H of the empty columns instead of G (RowArgs::zero_mask), and the main
-// launch of body i + 1 then walks past empty half tiles (ColArgs::h_prezeroed), where the plan of body i + 1 says all of this:
-// the half-width kernel with the scan's flags (a current scan, no weight written behind it, no column list, at most five
-// slots: column_launch), the instance that reads them (PHASE 0, 4096 rows), every empty-column switch on, and nothing else in
-// the body that reads or writes gh -- no second pass, Nogrette sum, pre-pass or in-pass statistics.  Pure, like the plan: the
-// engine asks it of the NEXT body's plan ahead of the closing row launch and of the body's own plan ahead of its column launch.
-inline bool prezero_ok(const ColumnPlan& cp, const PassFacts& f) {
-    const Tuning& t = f.tun;
-    const ColLaunch& l = cp.main;
-    if (f.elem != 4 || f.Ph != 4096) return false;
-    if (l.family != ColFamily::tile2 || !l.col_flags || l.phase_mode != 0) return false;
-    if (!t.empty_col_inverse || !t.empty_col_forward || !t.empty_col_prezero) return false;
-    if (cp.second_pass || cp.nog || cp.presum || cp.presum_col || cp.dilated_forward || cp.noise_inverse_grid || l.stats || f.stat_groups) return false;
-    return cp.join == RowJoin::none;
+// ---- the row launch that closes a body ------------------------------------------------------------------------------
+// load / store: 0 = every column, 1 = active columns, 2 = active columns dilated by the spot windows
+struct RowClose {
+    int mode = 0;                   // row_kernel MODE (3 = MODE 2 that also writes the phase; float32 only)
+    bool finalize = false;          // one extra block folds the weight-norm partials into wscale
+    bool wslot_fold = false;        // ... those the column launch left per half tile (ColLaunch::wslots)
+    int load_sparse = 0, store_sparse = 0;
+    int zero_par = -1;              // >= 0: RowArgs::zero_par -- the zero H of the empty columns is stored instead of their G
+};
+// cp / f: the body it closes; next: the facts of the body after it as that body will form them itself (nothing between this
+// launch and that plan changes them), or null after the last body of a call.  Zeros are stored only where the next body
+// accepts them and consults no column scan that could change the flags they were stored by; never by the last launch of a
+// call, which leaves G of every column.
+inline RowClose plan_row_close(const ColumnPlan& cp, const PassFacts& f, const PassFacts* next) {
+    const bool sp = f.sparse_enabled;
+    const int store_sparse = (f.stat_groups & 2) ? 2 : 1;
+    RowClose rc;
+    rc.mode = next ? 2 : cp.last_mode;
+    rc.finalize = cp.finalize;
+    rc.wslot_fold = cp.finalize && !cp.second_pass && cp.main.wslots;
+    rc.load_sparse = sp ? 1 : 0;
+    rc.store_sparse = (rc.mode == 3 || !sp) ? 0 : store_sparse;
+    if (next && f.elem == 4 && !sp && cp.join == RowJoin::none) {
+        const ColumnPlan cpn = plan_column_pass(*next);
+        const Scans sn = scans_needed(*next);
+        if (cpn.accepts_prezeroed && !sn.noise && !sn.signal && !sn.flags) rc.zero_par = (f.r0 - cpn.main.shift) & 1;
+    }
+    return rc;
 }
-// ... and that launch walks the positions of the scan's tile list (ColArgs::tile_list) instead of every tile
-inline bool tile_list_ok(const ColumnPlan& cp, const PassFacts& f) { return prezero_ok(cp, f) && f.tun.empty_col_list != 0; }
 
-// The launches whose weight-norm partials are one slot per (hologram, tile, half, wave) in a buffer of their own
-// (ColArgs::wslots, tile_flags.hpp) instead of one per workgroup in wpartial: the updating launches of the instances of
-// col_tile2_kernel that can receive column flags (WTBUF: 4096 rows, at most five slots, PHASE 0; the register form of a batch
-// or the parked few-active form of one hologram -- launch_tile2_n picks by exactly these facts).  The sum then no longer depends
-// on which workgroup took which half tile.  The engine asks it for the column launch and for the fold of the row launch behind it.
-inline bool wslots_ok(const ColLaunch& l, const PassFacts& f) {
-    if (f.elem != 4 || f.Ph != 4096 || l.family != ColFamily::tile2) return false;
-    if (l.phase_mode != 0 || l.nr > 5 || !l.do_update) return false;
-    return f.B > 1 || l.few_active;
+// ---- the column scan ahead of dense launches ---------------------------------------------------------------------------
+// Dense launches at 4096 rows in float32: how many columns hold anything picks the instance of the half-width tile kernel for
+// one hologram (ColLaunch::few_active), and says in which columns that kernel requests weights and targets at all (col_flags;
+// batches pay the scan for this alone, unless MRAF keeps them off that kernel) -- a fact about the target, scanned once per upload.
+// rescan_outside: weights written behind the scan's back since are scanned again, once (PassFacts::w_outside_scan).
+struct DenseScan { bool scan, rescan_outside; };
+inline DenseScan dense_scan_needed(const PassFacts& f) {
+    const bool scan = f.elem == 4 && f.tun.tile2 && f.Ph == 4096 && (f.B == 1 || (f.tun.empty_col_loads && !f.mraf_enabled));
+    return DenseScan{scan, scan && f.tun.empty_col_loads != 0};
 }
 
 // spot feedback on a sparse target (Engine::iterate_spot_sparse): the fused launch over the spot columns, weight update off

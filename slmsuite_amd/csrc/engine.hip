@@ -366,7 +366,7 @@ template <typename R> struct Engine : EngineBase {
     DevBuf<unsigned short> sig_rows;    // [B][Pw] register slots of a column that hold signal pixels (scan_active_cols; col_presum_kernel)
     ColList active;                     // any bit of col_active
     // col_tile2_kernel, flag-reading instances: the ascending tiles that hold anything per hologram and how many (built with the
-    // scan, refresh_sparse), and the weight-norm slots per (hologram, tile, half, wave) of their updating launches (wslots_ok).
+    // scan, refresh_sparse), and the weight-norm slots per (hologram, tile, half, wave) of their updating launches (ColLaunch::wslots).
     // A slot of an EMPTY half tile reads +0 for as long as the scan is current: the buffer is cleared where it is made and with
     // every scan, a launch that walks past the half tile never writes it, and one that visits it (no flags, an option off)
     // sums the squares of weights that are all zero -- every pixel of such a column leaves the rule at wave_all_zero.
@@ -1212,17 +1212,20 @@ template <typename R> struct Engine : EngineBase {
         }
         return a;
     }
-    // load / store: 0 = every column, 1 = active columns, 2 = active columns dilated by the spot windows
-    // mode: row_kernel MODE (3 = MODE 2 that also writes the phase; float32 only)
+    // a row launch outside a loop body: nothing folded, every column read (store: as RowClose::store_sparse)
+    static RowClose plain_row(int mode, int store_sparse = 0) {
+        RowClose rc;
+        rc.mode = mode; rc.store_sparse = store_sparse;
+        return rc;
+    }
+    // rc: what the launch does (column_plan.hpp, plan_row_close)
     // cp: the column pass this launch closes (the partials it folds, the join of a single-pass MRAF body), or null
-    // zero_par: -1, or RowArgs::zero_par of a MODE 2 launch inside a call that stores the zero H of the columns the scan found
-    // empty instead of their G (the next body's column launch walks past them: ColArgs::h_prezeroed)
-    int run_row(int mode, bool finalize, int load_sparse = 0, int store_sparse = 0, const ColumnPlan* cp = nullptr, int zero_par = -1) {
+    int run_row(const RowClose& rc, const ColumnPlan* cp = nullptr) {
         state.row_launch_begins();
-        int r_ = run_row_impl(mode, finalize, load_sparse, store_sparse, cp, zero_par);
+        int r_ = run_row_impl(rc, cp);
         // gh holds G of the columns this launch stored -- of none that a later call may count on where it stored zeros instead
         // (an error return in mid-loop must not leave a G behind that is none)
-        if (r_ == 0) state.row_stored_g(mode, zero_par >= 0 ? -1 : store_sparse);
+        if (r_ == 0) state.row_stored_g(rc.mode, rc.zero_par >= 0 ? -1 : rc.store_sparse);
         return r_;
     }
     // (fused loops only; p = the plan of the call's first iteration)
@@ -1236,16 +1239,15 @@ template <typename R> struct Engine : EngineBase {
         return 0;
     }
     bool gh_holds(int need) const { return state.gh_holds(need, tun.keep_g != 0); }
-    int run_row_impl(int mode, bool finalize, int load_sparse, int store_sparse, const ColumnPlan* cp, int zero_par = -1) {
+    int run_row_impl(const RowClose& rc, const ColumnPlan* cp) {
+        const int mode = rc.mode, zero_par = rc.zero_par;
+        const bool finalize = rc.finalize;
         return timed(HGS_K_ROW, [&]() -> int {
             RowArgs<R> a = row_args(finalize, cp ? cp->wpartial_n : 0);
-            // the partials of a launch that left them per half tile (the same predicate as ahead of the column launch): the
-            // row-less block folds the hologram's WHOLE slot range
-            if (finalize && cp && !cp->second_pass && wslots_ok(cp->main, base_facts())) {
-                a.wpartial = wslots; a.n_wpartial = tile2_wslots(g.Pw); a.wslot_fold = 1;
-            }
-            a.load_mask = load_sparse == 1 ? active.mask.get() : load_sparse == 2 ? dilated.mask.get() : nullptr;
-            a.store_mask = store_sparse == 1 ? active.mask.get() : store_sparse == 2 ? dilated.mask.get() : nullptr;
+            // the partials of a launch that left them per half tile: the row-less block folds the hologram's WHOLE slot range
+            if (rc.wslot_fold) { a.wpartial = wslots; a.n_wpartial = tile2_wslots(g.Pw); a.wslot_fold = 1; }
+            a.load_mask = rc.load_sparse == 1 ? active.mask.get() : rc.load_sparse == 2 ? dilated.mask.get() : nullptr;
+            a.store_mask = rc.store_sparse == 1 ? active.mask.get() : rc.store_sparse == 2 ? dilated.mask.get() : nullptr;
             if (zero_par >= 0) {
                 if (sizeof(R) != 4 || mode != 2 || a.load_mask || a.store_mask || (cp && cp->join != RowJoin::none))
                     return fail(HGS_ERR_STATE, "zero-masked row launch outside a plain fp32 MODE 2 launch");
@@ -1411,7 +1413,7 @@ template <typename R> struct Engine : EngineBase {
         if (int e = need_ff()) return e;
         if (store_pff) { if (int e = need_pff()) return e; }
         // (a fused loop that ended on its dense row launch left G of every column behind: the transform starts with its column pass)
-        if (!gh_holds(0)) { if (int e = run_row(0, false)) return e; }
+        if (!gh_holds(0)) { if (int e = run_row(plain_row(0))) return e; }
         int r = timed(HGS_K_COL_FWD, [&]() -> int {
             ColArgs<R> a = col_args();
             a.store_pff = store_pff;
@@ -1430,7 +1432,7 @@ template <typename R> struct Engine : EngineBase {
         if (general) return f2n_general(false);
         if (!ff || !state.farfield_valid()) return fail(HGS_ERR_STATE, "no farfield to transform back");
         if (int e = inverse_columns()) return e;
-        return run_row(1, false);
+        return run_row(plain_row(1));
     }
     // the column half of the inverse transform, every column: ff -> gh
     int inverse_columns() {
@@ -1941,9 +1943,7 @@ template <typename R> struct Engine : EngineBase {
         }
     }
     // one launch of the column pass; then_scale: wscale = 1/||w'|| from its partials right after it (reduce_to_scale)
-    // prezeroed: the row launch immediately before, in this call, stored the zeros of the empty columns (prezero_ok)
-    // list_walk: ... and this launch walks the scan's tile list (tile_list_ok)
-    int launch_column(const ColLaunch& l, const CParams<R>& cprm, bool then_scale = false, bool prezeroed = false, bool list_walk = false) {
+    int launch_column(const ColLaunch& l, const CParams<R>& cprm, bool then_scale = false) {
         return timed(HGS_K_COL_FUSED, [&]() -> int {
             ColArgs<R> a = col_args();
             a.cp = cprm;
@@ -1964,15 +1964,13 @@ template <typename R> struct Engine : EngineBase {
             }
             if (l.listed) { a.col_list = active.list; a.n_active = active.n_dev; }
             a.list_xmap = l.list_xmap ? 1 : 0;
-            if (l.col_flags) {
-                a.col_flags = col_active;
-                a.zero_inv = tun.empty_col_inverse ? 1 : 0;
-                a.zero_fwd = (a.zero_inv && tun.empty_col_forward) ? 1 : 0;      // (the forward skip rests on the inverse skip)
-                a.h_prezeroed = (a.zero_fwd && prezeroed) ? 1 : 0;
-                if (a.h_prezeroed && list_walk && tile_list && tile_list_n) { a.tile_list = tile_list; a.tile_list_n = tile_list_n; }
-            }
+            if (l.col_flags) a.col_flags = col_active;
+            a.zero_inv = l.empty.skip_inverse ? 1 : 0;
+            a.zero_fwd = l.empty.skip_forward ? 1 : 0;
+            a.h_prezeroed = l.empty.prezeroed ? 1 : 0;
+            if (l.empty.list_walk && tile_list && tile_list_n) { a.tile_list = tile_list; a.tile_list_n = tile_list_n; }
             // weight-norm partials per half tile instead of per workgroup; the row launch behind it folds them (run_row_impl)
-            if (wslots_ok(l, base_facts())) {
+            if (l.wslots) {
                 if (then_scale) return fail(HGS_ERR_STATE, "weight-norm slots ahead of a per-workgroup reduction");
                 if (!wslots) { if (int e = clear_wslots()) return e; }
                 a.wslots = wslots;
@@ -2025,7 +2023,7 @@ template <typename R> struct Engine : EngineBase {
         state.spot_sparse_call_begins();
         Plan p = plan_iteration(st, hist ? hist : nullptr);
         if (int e = keep_prev_phase(p, n)) return e;
-        if (!gh_holds(windows_needed(p) ? 2 : 1)) { if (int e = run_row(0, false, 0, windows_needed(p) ? 2 : 1)) return e; }
+        if (!gh_holds(windows_needed(p) ? 2 : 1)) { if (int e = run_row(plain_row(0, windows_needed(p) ? 2 : 1))) return e; }
         for (int i = 0; i < n; ++i) {
             state.column_pass_begins();
             if (p.use_fixed || p.store_phase) { if (int e = need_pff()) return e; }
@@ -2057,7 +2055,9 @@ template <typename R> struct Engine : EngineBase {
                 store_next = windows_needed(pn) ? 2 : 1;
             }
             const bool last = i + 1 == n;
-            if (int e = run_row(last ? cp.last_mode : 2, false, 1, (last && cp.last_mode == 3) ? 0 : store_next, &cp)) return e;
+            RowClose rc = plain_row(last ? cp.last_mode : 2, (last && cp.last_mode == 3) ? 0 : store_next);
+            rc.load_sparse = 1;
+            if (int e = run_row(rc, &cp)) return e;
             p = pn;
         }
         return 0;
@@ -2097,13 +2097,9 @@ template <typename R> struct Engine : EngineBase {
             // single-pass MRAF: which columns hold a NaN target (the noise part exists only there) -- a fact about the
             // target, scanned once per upload; the dense launches themselves still walk every column
             if (int e = refresh_sparse()) return e;
-        } else if (sizeof(R) == 4 && tun.tile2 && g.Ph == 4096 && (B == 1 || (tun.empty_col_loads && !st->mraf_enabled))) {
-            // dense launches of one hologram at 4096 rows: how many columns hold anything picks the instance of the half-width
-            // tile kernel (ColArgs::few_active) -- a fact about the target, scanned once per upload
-            // (batches: the same scan says in which columns that kernel requests weights and targets at all; they now pay it
-            //  too -- one scan launch and a device-to-host synchronisation per upload of weights or target, dense images included)
-            // (weights written behind the scan's back since are scanned again here, once: EngineState::w_outside_scan)
-            if (tun.empty_col_loads) state.rescan_if_written_outside();
+        } else if (const DenseScan ds = dense_scan_needed(pass_facts(st, Plan{0, 0, 0}, false)); ds.scan) {
+            // one scan launch and a device-to-host synchronisation per upload of weights or target, dense images included
+            if (ds.rescan_outside) state.rescan_if_written_outside();
             if (int e = refresh_sparse()) return e;
         }
         // "computational_spot" statistics on the sparse path: amp_ff is produced on the spot columns dilated
@@ -2120,7 +2116,7 @@ template <typename R> struct Engine : EngineBase {
         Plan p = plan_iteration(st, hist ? hist : nullptr);
         if (int e = keep_prev_phase(p, n)) return e;
         // (the previous call may have left G of these columns behind: gh_state, row_kernel MODE 3)
-        if (!gh_holds(sp ? store_sparse : 0)) { if (int e = run_row(0, false, 0, sp ? store_sparse : 0)) return e; }
+        if (!gh_holds(sp ? store_sparse : 0)) { if (int e = run_row(plain_row(0, sp ? store_sparse : 0))) return e; }
         // the row launch that closed the body before, in THIS call, stored zeros in the empty columns of gh (never kept across
         // calls: the last launch of a call leaves G of every column)
         bool gh_prezeroed = false;
@@ -2134,20 +2130,19 @@ template <typename R> struct Engine : EngineBase {
             if (scans.signal) { if (int e = refresh_signal()) return e; }
             if (scans.flags) { if (int e = refresh_sparse()) return e; }         // (clean unless the weights / target moved)
             if (scans.noise || scans.signal || scans.flags) f = pass_facts(st, p, sp);
+            // (flags cannot change inside a call; a body that scans them again takes the plain form, which writes the same zeros)
+            f.gh_prezeroed = gh_prezeroed && !scans.flags;
             ColumnPlan cp = plan_column_pass(f);
             if (int e = acquire(cp, f)) return e;
-            // (flags cannot change inside a call; a body that scans them again takes the plain form, which writes the same zeros)
-            if (scans.flags) gh_prezeroed = false;
             // the row launch before decided on the plan of THIS body (same pure function, same facts): where it stored zeros,
             // this launch must be the one that counts on them -- any other would read them as G
-            if (gh_prezeroed && !prezero_ok(cp, f)) return fail(HGS_ERR_STATE, "zero-masked G ahead of a column pass that reads every column");
+            if (f.gh_prezeroed && !cp.accepts_prezeroed) return fail(HGS_ERR_STATE, "zero-masked G ahead of a column pass that reads every column");
             // execute
             const CParams<R> cprm = cparams(st, p);
             if (cp.dilated_forward) { if (int e = launch_dilated_forward()) return e; }
             if (int e = launch_prepass(cp, cprm)) return e;
             if (cp.nog) { if (int e = launch_column(cp.nog_pass, cprm)) return e; }
-            if (int e = launch_column(cp.main, cprm, cp.scale_after_main, gh_prezeroed, gh_prezeroed && tile_list_ok(cp, f))) return e;
-            gh_prezeroed = false;
+            if (int e = launch_column(cp.main, cprm, cp.scale_after_main)) return e;
             if (cp.second_pass) { if (int e = launch_column(cp.second, cprm)) return e; }
             if (int e = launch_noise_inverse(cp)) return e;
             if (stat_ctx) { if (int e = fused_stats_finish(i, cp)) return e; }
@@ -2157,23 +2152,14 @@ template <typename R> struct Engine : EngineBase {
             st->iter++;
             Plan pn{0, 0, 0};
             if (i + 1 < n) pn = plan_iteration(st, hist ? hist + i + 1 : nullptr);
-            // the row launch that closes the iteration: on the sparse path it reads the active columns and writes those the
-            // next column launches read; the last one of the call extracts the phase (cp.last_mode)
+            // the row launch that closes the iteration (plan_row_close): on the sparse path it reads the active columns and writes
+            // those the next column launches read; the last one of the call extracts the phase.  The next body's facts are those it
+            // will form itself: nothing between here and there changes them.
             const bool last = i + 1 == n;
-            // HGS_OPT_EMPTY_COL_PREZERO: where the NEXT body's main launch is the half-width kernel with the scan's flags and
-            // nothing else of that body touches gh (prezero_ok on its plan -- the facts are those it will form itself: nothing
-            // between here and there changes them, and no scan runs for such a body), this launch stores the zero H of the
-            // empty columns instead of their G, which that launch would not read.  Never the last launch of a call.
-            int zero_par = -1;
-            if (!last && sizeof(R) == 4 && cp.join == RowJoin::none && !sp) {
-                const PassFacts fn = pass_facts(st, pn, sp);
-                const ColumnPlan cpn = plan_column_pass(fn);
-                const Scans sn = scans_needed(fn);
-                if (prezero_ok(cpn, fn) && !sn.noise && !sn.signal && !sn.flags) zero_par = (g.r0 - cpn.main.shift) & 1;
-            }
-            if (int e = run_row(last ? cp.last_mode : 2, cp.finalize, sp ? 1 : 0, (last && cp.last_mode == 3) ? 0 : (sp ? store_sparse : 0), &cp, zero_par))
-                return e;
-            gh_prezeroed = zero_par >= 0;
+            const PassFacts fn = pass_facts(st, pn, sp);
+            const RowClose rc = plan_row_close(cp, f, last ? nullptr : &fn);
+            if (int e = run_row(rc, &cp)) return e;
+            gh_prezeroed = rc.zero_par >= 0;
             p = pn;
         }
         return 0;

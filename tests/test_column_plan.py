@@ -7,45 +7,15 @@ SAYS; the GPU dispatch tests keep asserting what was LAUNCHED.
 Device facts are inputs: 256 CUs and the block counts hgs_create derives from them (tests/column_plan_host.cpp,
 derive_blocks).  Geometry as the Python classes make it: a centred SLM block, r0 = (Ph - Sh) // 2.
 """
-import json
 import os
-import shutil
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GS, LEONARDO, KIM, NOGRETTE, WU, TANH = range(6)
-
-
-def _compiler():
-    for cxx in ("c++", "clang++", "/opt/rocm/llvm/bin/clang++", "/opt/rocm/bin/amdclang++"):
-        path = shutil.which(cxx)
-        if path:
-            return path
-    return None
-
-
-@pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler (c++ / clang++) on this machine")
-    exe = str(tmp_path_factory.mktemp("column_plan") / "column_plan_host")
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "slmsuite_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "column_plan_host.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+from plan_host import GS, KIM, LEONARDO, NOGRETTE, ROOT, TANH, WU, host, plan  # noqa: F401  (host: the fixture)
 
 
 def _plan(exe, **facts):
-    if "Sh" in facts and "r0" not in facts:
-        facts["r0"] = (facts["Ph"] - facts["Sh"]) // 2
     facts.setdefault("Pw", facts["Ph"])
-    line = " ".join(f"{k}={int(v)}" for k, v in facts.items())
-    r = subprocess.run([exe, "plan"], input=line + "\n", capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return json.loads(r.stdout)
+    return plan(exe, **facts)
 
 
 # a dense image whose columns were scanned (HGS_OPT_SPARSE_COLUMNS = 1 finds every column active): what Hologram(...) gives
@@ -204,6 +174,36 @@ def test_column_lists_and_tile_switches(host):
     _sub(_plan(host, **_image(4096, 1032, do_update=1, HGS_KEEP_G=0)), last_mode=1)
 
 
+def test_row_close_between_bodies_of_the_headline(host):
+    """plan_row_close on the cfg-2-like body: zeros for the empty columns between two such bodies, never from the last launch
+    of a call (it leaves G of every column, MODE 3), never ahead of a WGS-Kim body that stores the farfield phase."""
+    middle = plan(host, preset="cfg2")["close_next"]
+    last = plan(host, preset="cfg2")["close_last"]
+    before_kim = plan(host, preset="cfg2", method=KIM, next=dict(store_phase=1))["close_next"]
+    assert middle["zero_par"] >= 0 and last["zero_par"] == -1 and before_kim["zero_par"] == -1
+    _sub(middle, mode=2, finalize=1, wslot_fold=1, load_sparse=0, store_sparse=0, zero_par=0)     # (r0 = shift = 1472)
+    _sub(last, mode=3, finalize=1, wslot_fold=1, load_sparse=0, store_sparse=0)
+    _sub(before_kim, mode=2, finalize=1, wslot_fold=1, load_sparse=0, store_sparse=0)
+    # the body that finds the zeros: walks past empty half tiles along the scan's list; one that finds none does neither
+    _sub(plan(host, preset="cfg2", gh_prezeroed=1)["main"]["empty"], skip_inverse=1, skip_forward=1, prezeroed=1, list_walk=1)
+    _sub(plan(host, preset="cfg2")["main"]["empty"], skip_inverse=1, skip_forward=1, prezeroed=0, list_walk=0)
+    # a column list: masks on both sides, the spot statistics' dilated columns stored; MODE 3 stores every column
+    lst = dict(elem=4, Ph=1024, Sh=288, B=1, method=LEONARDO, do_update=1, sparse_enabled=1, n_active_min=8, n_active_max=8)
+    _sub(_plan(host, **lst)["close_next"], mode=2, load_sparse=1, store_sparse=1, zero_par=-1, wslot_fold=0)
+    _sub(_plan(host, stat_groups=2, **lst)["close_next"], load_sparse=1, store_sparse=2)
+    _sub(_plan(host, **lst)["close_last"], mode=3, load_sparse=1, store_sparse=0)
+    _sub(_plan(host, HGS_KEEP_G=0, **lst)["close_last"], mode=1, load_sparse=1, store_sparse=1)
+
+
+def test_dense_scan_per_upload(host):
+    """The scan ahead of dense launches: fp32 at 4096 rows with the half-width kernel; one hologram always (it picks the
+    few-active instance), a batch for the column flags alone -- not with the loads switch off or under MRAF."""
+    for facts, scan, rescan in ((dict(), 1, 1), (dict(B=8), 1, 1), (dict(HGS_OPT_EMPTY_COL_LOADS=0), 1, 0), (dict(B=8, HGS_OPT_EMPTY_COL_LOADS=0), 0, 0),
+                                (dict(B=8, mraf=1), 0, 0), (dict(mraf=1), 1, 1), (dict(HGS_TILE2=0), 0, 0), (dict(elem=8), 0, 0),
+                                (dict(Ph=2048, Sh=520), 0, 0), (dict(Ph=8192, Pw=8192, Sh=2304), 0, 0)):
+        assert plan(host, preset="cfg2", **facts)["dense_scan"] == dict(scan=scan, rescan_outside=rescan), facts
+
+
 def test_invariants_over_a_swept_grid_of_facts(host):
     """Element size x padded rows x SLM rows x batch x method x MRAF x update x phase mode x statistics x column policy x
     w_unit x noise / signal columns, with every A/B switch off in turn.  Each invariant is a guard or a comment of the engine:
@@ -212,7 +212,13 @@ def test_invariants_over_a_swept_grid_of_facts(host):
     and only if a split form ran; MODE 3 as the last row launch only for 4-byte elements without a join; every grid within
     max(col_blocks, tile_blocks, 3 x #CU) per hologram (what wpartial, dpartial and the statistics partials are sized for);
     exactly one of {two passes, tile split, column split, tile pre-sum, column pre-sum} per MRAF update and none otherwise;
-    the weight norm folded exactly once per update; every form preceded by the column scan it consults."""
+    the weight norm folded exactly once per update; every form preceded by the column scan it consults; no weight-norm slots
+    ahead of a per-workgroup reduction (scale_after_main); each empty-column level only on the one below it (list walk, zeros
+    in place, forward skipped, inverse skipped, the scan's flags), none of them nor the slots outside tile2 or outside the main
+    launch where they count on the row launch before; the closing row launch stores zeros only between two bodies, as a plain
+    MODE 2 launch without masks or a join, and only for a next body whose plan accepts them.  The column policies include dense
+    launches with few active columns (the flags go with the launch), with zeros left ahead of every body that accepts them
+    and with a weight written behind the scan."""
     r = subprocess.run([host, "sweep"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     tail = r.stdout.strip().splitlines()

@@ -1,45 +1,19 @@
 """
-``prezero_ok`` of ``slmsuite_amd/csrc/column_plan.hpp`` without a GPU: the pure predicate that says whether the row launch ahead
-of a body may store the zero H of the empty columns instead of their G (``RowArgs::zero_mask``) and the body's column launch may
-walk past empty half tiles (``ColArgs::h_prezeroed``).  ``tests/column_plan_prezero_host.cpp`` forms the facts of a body, plans
-it with ``plan_column_pass`` and prints the predicate; the table below names every fact that must turn it off.
+``ColumnPlan::accepts_prezeroed`` of ``slmsuite_amd/csrc/column_plan.hpp`` without a GPU: whether the row launch ahead of a body
+may store the zero H of the empty columns instead of their G (``RowArgs::zero_mask``) and the body's column launch may walk past
+empty half tiles (``ColArgs::h_prezeroed``).  ``tests/column_plan_host.cpp`` forms the facts of a cfg-2-like body and plans it with
+``plan_column_pass``; the table below names every fact that must turn the field off.
 """
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GS, LEONARDO, KIM, NOGRETTE = range(4)
-
-
-def _compiler():
-    for cxx in ("c++", "clang++", "/opt/rocm/llvm/bin/clang++", "/opt/rocm/bin/amdclang++"):
-        path = shutil.which(cxx)
-        if path:
-            return path
-    return None
-
-
-@pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler (c++ / clang++) on this machine")
-    exe = str(tmp_path_factory.mktemp("column_plan_prezero") / "column_plan_prezero_host")
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "slmsuite_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "column_plan_prezero_host.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+from plan_host import GS, KIM, LEONARDO, NOGRETTE, host, plan  # noqa: F401  (host: the fixture)
 
 
 def _ask(exe, **facts):
-    line = " ".join(f"{k}={int(v)}" for k, v in facts.items())
-    r = subprocess.run([exe], input=line + "\n", capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    ok, family, col_flags, phase_mode = r.stdout.split()
-    return dict(ok=int(ok), family=family, col_flags=int(col_flags), phase_mode=int(phase_mode))
+    p = plan(exe, preset="cfg2", **facts)
+    main = p["main"]
+    return dict(ok=p["accepts_prezeroed"], family=main["family"] if main["family"] == "tile2" else "other", col_flags=main["col_flags"],
+                phase_mode=main["phase_mode"])
 
 
 def test_true_for_the_headline_and_the_batch(host):
@@ -91,3 +65,8 @@ def test_the_switch_alone_changes_no_plan(host):
     on, off = _ask(host), _ask(host, HGS_OPT_EMPTY_COL_PREZERO=0)
     assert on["ok"] == 1 and off["ok"] == 0
     assert {k: v for k, v in on.items() if k != "ok"} == {k: v for k, v in off.items() if k != "ok"}
+    # ... in every field of the plan; only the row launch ahead of such a body stops storing the zeros
+    on, off = plan(host, preset="cfg2"), plan(host, preset="cfg2", HGS_OPT_EMPTY_COL_PREZERO=0)
+    assert on["close_next"]["zero_par"] >= 0 and off["close_next"]["zero_par"] == -1
+    off["accepts_prezeroed"], off["close_next"]["zero_par"] = on["accepts_prezeroed"], on["close_next"]["zero_par"]
+    assert on == off

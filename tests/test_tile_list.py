@@ -7,51 +7,21 @@ grids of 2 - 16 workgroups over every flag row of 1 - 5 tiles, every empty / non
 and compares with the flag words and with the static walk (``tile2_next_nonempty``); it is built as the stand-alone program
 it is, with AddressSanitizer and UndefinedBehaviorSanitizer.  Nothing is loaded into Python.
 
-``wslots_ok`` (which launches leave their weight-norm partials per half tile) and ``tile_list_ok`` (which walk the list) of
-``column_plan.hpp`` are asked through ``tests/column_plan_wslots_host.cpp`` on the cases ``test_column_plan_prezero.py`` asks
-``prezero_ok``.
+``ColLaunch::wslots`` (which launches leave their weight-norm partials per half tile) and ``EmptyCols::list_walk`` (which walk the
+list where the row launch before left the zeros) of ``column_plan.hpp`` are read from the plan ``tests/column_plan_host.cpp``
+prints, on the cases ``test_column_plan_prezero.py`` asks ``accepts_prezeroed``.
 """
 import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "slmsuite_amd", "csrc")
-GS, LEONARDO, KIM, NOGRETTE = range(4)
-
-
-def _compiler():
-    for cxx in ("c++", "clang++", "/opt/rocm/llvm/bin/clang++", "/opt/rocm/bin/amdclang++"):
-        path = shutil.which(cxx)
-        if path:
-            return path
-    return None
+from plan_host import CSRC, GS, KIM, LEONARDO, NOGRETTE, build, host, plan  # noqa: F401  (host: the fixture)
 
 
 @pytest.fixture(scope="module")
 def walk_host(tmp_path_factory):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler (c++ / clang++) on this machine")
-    exe = str(tmp_path_factory.mktemp("tile_list") / "tile_list_host")
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-I", CSRC, os.path.join(ROOT, "tests", "tile_list_host.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
-@pytest.fixture(scope="module")
-def plan_host(tmp_path_factory):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler (c++ / clang++) on this machine")
-    exe = str(tmp_path_factory.mktemp("column_plan_wslots") / "column_plan_wslots_host")
-    r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC,
-                        os.path.join(ROOT, "tests", "column_plan_wslots_host.cpp"), "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return build(tmp_path_factory, "tile_list_host", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
 
 
 def test_list_walk_visits_every_non_empty_half_tile_once(walk_host):
@@ -75,25 +45,29 @@ def test_kernel_walks_the_list_through_the_helper_only():
 
 
 def _ask(exe, **facts):
-    line = " ".join(f"{k}={int(v)}" for k, v in facts.items())
-    r = subprocess.run([exe], input=line + "\n", capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    slots, listed, prezero, family, col_flags, few, grid = r.stdout.split()
-    return dict(slots=int(slots), list=int(listed), prezero=int(prezero), family=family, col_flags=int(col_flags), few=int(few), grid=int(grid))
+    """The cfg-2-like body behind a row launch that left the zeros wherever the body accepts them (the engine never leaves them
+    ahead of another): whether it leaves slots, walks the list, accepts the zeros."""
+    p = plan(exe, preset="cfg2", **facts)
+    if p["accepts_prezeroed"]:
+        p = plan(exe, preset="cfg2", gh_prezeroed=1, **facts)
+    main = p["main"]
+    assert main["empty"]["prezeroed"] == p["accepts_prezeroed"]
+    return dict(slots=main["wslots"], list=main["empty"]["list_walk"], prezero=p["accepts_prezeroed"],
+                family=main["family"] if main["family"] == "tile2" else "other", col_flags=main["col_flags"], few=main["few_active"], grid=main["grid"])
 
 
-def test_slots_and_list_for_the_headline_and_the_batch(plan_host):
+def test_slots_and_list_for_the_headline_and_the_batch(host):
     """cfg 2 and cfg 3: an updating body leaves slots and walks the list; a body without an update walks the list and leaves no
     partial at all.  The grid stays the planned one."""
     for batch, grid in ((1, 768), (8, 96)):
-        got = _ask(plan_host, B=batch)
+        got = _ask(host, B=batch)
         assert got == dict(slots=1, list=1, prezero=1, family="tile2", col_flags=1, few=1, grid=grid), (batch, got)
         for method, upd in ((LEONARDO, 0), (GS, 0), (KIM, 0)):
-            got = _ask(plan_host, B=batch, method=method, do_update=upd)
+            got = _ask(host, B=batch, method=method, do_update=upd)
             assert (got["slots"], got["list"], got["prezero"], got["grid"]) == (0, 1, 1, grid), (batch, method, got)
 
 
-# every prezero_ok case: (facts, wslots_ok, tile_list_ok, prezero_ok)
+# every accepts_prezeroed case: (facts, main.wslots, main.empty.list_walk, accepts_prezeroed)
 CASES = {
     "list off": (dict(HGS_OPT_EMPTY_COL_LIST=0), 1, 0, 1),
     "prezero off": (dict(HGS_OPT_EMPTY_COL_PREZERO=0), 1, 0, 0),
@@ -124,17 +98,17 @@ CASES = {
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
-def test_predicates(plan_host, name):
+def test_predicates(host, name):
     facts, slots, listed, prezero = CASES[name]
-    got = _ask(plan_host, **facts)
+    got = _ask(host, **facts)
     assert (got["slots"], got["list"], got["prezero"]) == (slots, listed, prezero), (name, got)
     assert got["list"] <= got["prezero"]            # the list never acts without the pre-zeroed H
     if got["slots"]:
         assert got["family"] == "tile2"
 
 
-def test_grid_override_changes_neither_predicate(plan_host):
+def test_grid_override_changes_neither_predicate(host):
     """HGS_TILE2_BLOCKS moves the grid and nothing else: the slots make the result independent of it."""
     for blocks, grid in ((16, 16), (528, 528), (752, 752), (0, 768)):
-        got = _ask(plan_host, HGS_TILE2_BLOCKS=blocks)
+        got = _ask(host, HGS_TILE2_BLOCKS=blocks)
         assert (got["slots"], got["list"], got["prezero"], got["grid"]) == (1, 1, 1, grid), (blocks, got)
